@@ -10,6 +10,17 @@ Envs auto-reset inside the step kernel when they die (the reference driver's
 `if done: env.reset()`).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4] [--obs packed|f32]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line:
+the headline (`value`, `ms_per_step`) and what follows from its own timing.
+--dump-outputs DIR also writes what the last timed step delivered (packed obs,
+reward, done; the float32 obs with --obs f32) as DIR/<name>.npy.  Everything
+else the benchmark measures -- the CPU baseline, the other configs, sizes and
+obs formats, the rollout and image kernels, the Python surfaces, the
+clear-heavy stream, the steady-state launches, the region probe and, at
+--gpus N > 1, the gather-free and decode-free repeats -- runs only with
+--full (the --no-* switches then drop single legs as before).
 
 --gpus N > 1: one process per GPU.  Run directly, bench.py starts the N rank
 processes itself (before anything touches a GPU) with the rendezvous on
@@ -20,8 +31,9 @@ timed step is BASELINE config C5's step: st_step_wire on every shard, the
 RCCL gather of every shard's packed obs/reward/done to rank 0, double-buffered
 (step t+1 computes into the other buffer while the gather of step t runs), and
 rank 0's decode of the gathered rows into the global obs / reward / done
-(st_unwire_shards).  The same steps without the decode (`gather.no_decode`)
-and without the gather (`step_no_gather`) are reported beside it.
+(st_unwire_shards).  With --full the same steps without the decode
+(`gather.no_decode`) and without the gather (`step_no_gather`) are reported
+beside it.
 Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
@@ -100,6 +112,33 @@ def rollout_bytes(width: int, height: int, p_lock: float, f32: bool, k: int) -> 
     step = 1 + 4 * width + 4 + 1 + (4 * width * height if f32 else 0)
     state = 2 * (4 * width + 15 * 4)
     return step + 23.7 * p_lock + state / k
+
+
+# ----------------------------------------------------------------------------- outputs
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes --dump-outputs may write in all
+
+
+def dump_outputs(dirname: str, arrays: dict) -> dict:
+    """--dump-outputs: write `arrays` (name -> (tensor, env axis)) as
+    dirname/<name>.npy -- float32 stays float32, integers and bools become
+    float64 (exact for 32-bit values).  Above DUMP_BUDGET bytes in all, every
+    array keeps the same fixed sample of envs (seed 0, ascending), whose
+    indices go to env_index.npy.  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, (x, axis) in arrays.items():
+        a = x.detach().cpu().numpy()
+        host[name] = (a if a.dtype == np.float32 else a.astype(np.float64), axis)
+    n = next(a.shape[axis] for a, axis in host.values())
+    per_env = sum(a.nbytes // n for a, _ in host.values())
+    if n * per_env > DUMP_BUDGET:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_BUDGET // (per_env + 8), replace=False))
+        host = {name: (np.take(a, keep, axis=axis), axis) for name, (a, axis) in host.items()}
+        host["env_index"] = (keep.astype(np.float64), 0)
+    for name, (a, _) in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, (a, _) in host.items()}
 
 
 # ----------------------------------------------------------------------------- PMC
@@ -336,12 +375,22 @@ def main():
                          "bit stream (8 words = 32 B per 10x20 env: the obs bits, the reward's 32 bits, done; "
                          "rank 0 decodes it inside the timed region) or st_step's obs/reward/done rows (48 B)")
     ap.add_argument("--rollout-chunk", type=int, default=100, help="steps per st_rollout launch")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the CPU baseline, the variants (other "
+                         "configs, sizes, obs formats, rollout / image kernels, Python surfaces, clear-heavy "
+                         "actions), the steady-state launches and the region probe, and at --gpus N > 1 the "
+                         "gather-free and decode-free repeats; without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's outputs (what a caller of the "
+                         "timed path receives: packed obs, reward, done; the float32 obs with --obs f32; at "
+                         "--gpus N > 1 rank 0's gathered global ones) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB in all (above that a fixed seeded sample of envs + env_index.npy)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (profiling passes)")
-    ap.add_argument("--no-clear-heavy", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no variants (profiling passes)")
+    ap.add_argument("--no-clear-heavy", action="store_true", help="with --full: skip the clear-heavy variant")
     ap.add_argument("--no-surfaces", action="store_true",
-                    help="skip the Python-surface timings (single_env, vec_env): PMC passes, whose "
+                    help="with --full: skip the Python-surface timings (single_env, vec_env): PMC passes, whose "
                          "per-kernel averages would otherwise mix in their launches")
     args = ap.parse_args()
 
@@ -553,7 +602,7 @@ def main():
             # region_probe's events, created and first recorded now (a first
             # record costs ~100 us of host time; creating them right before a
             # region slowed its first launch)
-            self.pevs = [torch.cuda.Event(enable_timing=True) for _ in range(K + 1)] if K <= 200 else []
+            self.pevs = [torch.cuda.Event(enable_timing=True) for _ in range(K + 1)] if (args.full and K <= 200) else []
             with torch.cuda.stream(s):
                 for e_ in self.pevs:
                     e_.record(s)
@@ -706,10 +755,11 @@ def main():
         def measure_gather(self):
             """C5's timed region: K x (st_step + gather to rank 0 + rank 0's
             decode of the gathered wire rows into the global obs / reward /
-            done) after WU such steps untimed; then the same K steps without
-            the decode, reported beside (`no_decode`).  Rank 0's decoded
-            outputs of the last timed step go to $ST_BENCH_DUMP (an .npz)
-            when set (tests compare them with the oracle)."""
+            done) after WU such steps untimed; with --full then the same K
+            steps without the decode, reported beside (`no_decode`).  Rank 0's
+            decoded outputs of the last timed step go to $ST_BENCH_DUMP (an
+            .npz) when set (tests compare them with the oracle) and to
+            --dump-outputs' directory."""
             self.setup_gather()
             with torch.cuda.stream(s):
                 self.gather_range(0, WU)
@@ -718,7 +768,7 @@ def main():
             el, ev_ms, p_lock = timed(self.eng, lambda: self.gather_range(WU, WU + K), K)
             ng, nd = self.ngathers - g0, self.ndecodes - d0
             dump = os.environ.get("ST_BENCH_DUMP")
-            if rank == 0 and dump:
+            if rank == 0 and (dump or args.dump_outputs):
                 import numpy as np
                 from gym_simpletetris_amd.distributed import assemble
                 if self.wire:  # the region's own last decode (st_unwire_shards)
@@ -727,8 +777,11 @@ def main():
                 else:
                     got = self.grecv[(WU + K - 1) & 1]
                     o, r, d = assemble([b.cpu() for b in got], W)
-                np.savez(dump, obs=o.numpy().view(np.uint32), reward=r.numpy(), done=d.numpy(),
-                         step=WU + K - 1, n_global=self.n_global, gathers_timed=ng, decodes_timed=nd)
+                if dump:
+                    np.savez(dump, obs=o.numpy().view(np.uint32), reward=r.numpy(), done=d.numpy(),
+                             step=WU + K - 1, n_global=self.n_global, gathers_timed=ng, decodes_timed=nd)
+                if args.dump_outputs:
+                    dump_outputs(args.dump_outputs, {"obs": (o, 1), "reward": (r, 0), "done": (d, 0)})
             bpr = self.gbufs[0].numel() * 4
             ms = el / K * 1e3
             out = {"value": self.n_global * K / el, "ms_per_step": ms, "event_ms_per_step": ev_ms / K,
@@ -745,7 +798,7 @@ def main():
                               "bytes_into_rank0_per_step": bpr * (world - 1),
                               "rank0_ingress_GBps": bpr * (world - 1) / (ms * 1e-3) / 1e9,
                               "overlap": "double-buffered: step t+1 computes while step t is gathered"}}
-            if self.wire:
+            if self.wire and args.full:
                 self.decode = False
                 el2, ev2, _ = timed(self.eng, lambda: self.gather_range(WU, WU + K), K)
                 self.decode = True
@@ -825,11 +878,19 @@ def main():
                             "state): host stamps only, then an event before every launch; debug, not value")
             return out
 
-        def measure(self, steady=True):
+        def measure(self, steady=True, dump=None):
+            """Warm-up, the timed K steps, then (dump: --dump-outputs'
+            directory) the last timed step's outputs as they lie in the
+            output buffers, before anything else steps into them."""
             self.warmup()
             run, keep = self.runner()
             el, ev_ms, p_lock = timed(self.eng, run, K)
             del keep
+            if dump:
+                arrs = {"obs": (self.sh._obs, 1), "reward": (self.sh._rew, 0), "done": (self.sh._done, 0)}
+                if self.f32:
+                    arrs["obs_f32"] = (self.obs_f32, 0)
+                dump_outputs(dump, arrs)
             probe = self.region_probe() if (steady and K <= 200 and args.launch == "eager") else None
             ev_us = ev_ms * 1e3 / K
             kname = kname_of("step", self.f32, self.sc0)
@@ -865,11 +926,14 @@ def main():
         # BASELINE C5: each timed step = st_step on every shard + the gather
         # of its outputs to rank 0; the same steps without the gather beside it
         gm = head.measure_gather()
-        ng = head.measure(steady=False)
-        hm = dict(gm, roofline=dict(ng["roofline"], note="st_step, the engine's kernel, from the "
-                                    "gather-free steps (step_no_gather); the gather's rate is in `gather`"))
+        if args.full:
+            ng = head.measure(steady=False)
+            hm = dict(gm, roofline=dict(ng["roofline"], note="st_step, the engine's kernel, from the "
+                                        "gather-free steps (step_no_gather); the gather's rate is in `gather`"))
+        else:
+            hm = dict(gm, roofline=None)  # st_step's own rate: the gather-free steps of --full
     else:
-        hm = head.measure()
+        hm = head.measure(steady=args.full, dump=args.dump_outputs)
     out = {
         "metric": METRIC,
         "value": hm["value"],
@@ -877,6 +941,7 @@ def main():
         "n_gpus": world,
         "steps": K,
         "warmup": WU,
+        "full": args.full,
         "ms_per_step": hm["ms_per_step"],
         "higher_is_better": True,
         "scaling": "weak",
@@ -918,9 +983,10 @@ def main():
     if use_dist:
         out["gather"] = hm["gather"]
         out["config"]["gathers_per_step"] = 1
+    if use_dist and args.full:
         out["step_no_gather"] = {k: ng[k] for k in ("value", "ms_per_step", "event_ms_per_step", "p_lock")}
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         variants = {}
         eng = head.eng
         L, ctx = eng._L, eng._ctx

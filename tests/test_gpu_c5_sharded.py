@@ -172,7 +172,7 @@ def test_bench_gpus8_direct_invocation(tmp_path):
     dump = tmp_path / "c5.npz"
     env = dict(os.environ, ST_BENCH_SHARED_GPU="1", ST_BENCH_DUMP=str(dump))
     env.pop("WORLD_SIZE", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--full",
                         "--steps", "20", "--warmup", "5", "--n-envs", "2048", "--no-cpu-baseline",
                         "--no-clear-heavy", "--no-surfaces"],
                        env=env, capture_output=True, text=True, timeout=300)

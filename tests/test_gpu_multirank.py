@@ -112,7 +112,7 @@ def test_bench_gpus2_direct_invocation(tmp_path):
     done rows; the 8-rank test covers the default wire format)."""
     env = dict(os.environ, ST_BENCH_SHARED_GPU="1", ST_BENCH_DUMP=str(tmp_path / "c5.npz"))
     env.pop("WORLD_SIZE", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--full",
                         "--steps", "30", "--warmup", "5", "--n-envs", "8192", "--no-cpu-baseline",
                         "--no-clear-heavy", "--gather-format", "rows"],
                        env=env, capture_output=True, text=True, timeout=110)
@@ -138,7 +138,7 @@ def test_bench_rccl_calls_one_rank(tmp_path):
     RCCL); the gathered outputs of the last timed step equal the oracle's."""
     env = dict(os.environ, ST_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_port()), ST_BENCH_DUMP=str(tmp_path / "c5.npz"))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "nccl",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "nccl", "--full",
                         "--steps", "30", "--warmup", "5", "--n-envs", "8192", "--no-cpu-baseline",
                         "--no-clear-heavy"],
                        env=env, capture_output=True, text=True, timeout=110)

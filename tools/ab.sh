@@ -4,10 +4,10 @@
 # within each round, so box drift hits every build alike.
 #
 # usage: tools/ab.sh MODE ROUNDS lib.so [lib.so ...]
-#   MODE step     bench.py --no-extras (eager st_step, 65,536 envs, C3) at
+#   MODE step     bench.py --full --no-extras (eager st_step, 65,536 envs, C3) at
 #                 K = 2000 and at the driver's K = 20
 #   MODE rollout  tools/ab_rollout.py (st_rollout, CH-step launches)
-#   MODE bench    bench.py with all variants (step, f32, rollouts)
+#   MODE bench    bench.py --full with all variants (step, f32, rollouts)
 #   MODE stamps   tools/stamps.py phase split (stamp builds: ST_STAMPS=1)
 # env: TAG (output name), AB_N (envs, rollout), AB_F32=1 (rollout f32 too),
 #      CH / L (rollout steps per launch / launches), STEPS / WARMUP (bench),
@@ -27,14 +27,14 @@ one() {  # one timing of library $1
   step)
     for K in 2000 20; do
       W=100; [ $K -eq 20 ] && W=5
-      ST_LIB="$lib" timeout -k 10 120 python bench.py --no-extras --no-cpu-baseline --steps $K --warmup $W \
+      ST_LIB="$lib" timeout -k 10 120 python bench.py --full --no-extras --no-cpu-baseline --steps $K --warmup $W \
         | python -c "import json,sys; d=json.load(sys.stdin); r=d['roofline']; print('%-20s K=%-5d us_per_step=%.3f event_us=%.3f steady_us=%.3f value=%.4g' % ('$name', $K, d['ms_per_step']*1e3, r['event_us_per_launch'], r['steady']['event_us_per_launch'], d['value']))" || return 1
     done ;;
   rollout)
     AB_N=${AB_N:-65536} ST_LIB="$lib" AB_LABEL="$name n=${AB_N:-65536}" \
       timeout -k 10 120 python tools/ab_rollout.py ${CH:-100} ${L:-10} ${AB_F32:+f32} || return 1 ;;
   bench)
-    ST_LIB="$lib" timeout -k 10 200 python bench.py --steps ${STEPS:-500} --warmup ${WARMUP:-50} --no-cpu-baseline \
+    ST_LIB="$lib" timeout -k 10 200 python bench.py --steps ${STEPS:-500} --warmup ${WARMUP:-50} --full --no-cpu-baseline \
       | python -c "import json,sys; d=json.load(sys.stdin); v=d['variants']; print('%-20s step=%.3f step_f32=%.3f rollout_packed=%.3f rollout_f32=%.3f us/step' % ('$name', d['ms_per_step']*1e3, v['step_f32']['ms_per_step']*1e3, v['rollout_packed']['ms_per_step']*1e3, v['rollout_f32']['ms_per_step']*1e3))" || return 1 ;;
   stamps)
     echo "== $name"; ST_LIB="$lib" timeout -k 10 200 python tools/stamps.py || return 1 ;;

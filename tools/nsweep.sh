@@ -5,7 +5,7 @@ set -o pipefail
 R="${GRAFT_REPO_ROOT:-/root/repo}"; cd "$R"; mkdir -p gpurun_out
 TAG=${TAG:-ns}
 for n in ${SIZES:-4096 16384 65536 262144 524288 1048576}; do
-  timeout -k 10 180 python bench.py --n-envs $n --steps ${STEPS:-1000} --warmup 50 --no-extras --no-cpu-baseline ${EXTRA} \
+  timeout -k 10 180 python bench.py --n-envs $n --steps ${STEPS:-1000} --warmup 50 --full --no-extras --no-cpu-baseline ${EXTRA} \
     | python -c "
 import json, sys
 d = json.load(sys.stdin)
