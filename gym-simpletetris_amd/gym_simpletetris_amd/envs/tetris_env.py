@@ -573,7 +573,8 @@ class TetrisVecEnv:
     for torch's allocator -- a reused slot is then written only after the
     work queued on that stream.  copy=False: they live in one of two output slots
     that alternate, so they are overwritten two steps later (an info object
-    kept longer takes a copy; the obs / reward / done tensors do not) -- the
+    kept longer takes a copy; the obs / reward / done tensors do not; a step
+    that raised -- a rejected action batch -- wrote nothing and does not count) -- the
     fast path, for loops that consume each step's outputs right away.
     reset(return_info=True) returns (obs, info) like the reference's
     reset (:405-411): the post-reset counters (time 0, score 0, the new
@@ -703,6 +704,7 @@ class TetrisVecEnv:
         eng = self.engine
         a, gated = eng._actions(actions, gate=True)
         s = eng._stream()
+        k0 = self._k
         if self.copy:  # this step's outputs, the caller's from now on
             slot, reused = self._pool.take(self._new_slot)
             if reused:
@@ -717,18 +719,26 @@ class TetrisVecEnv:
                 held._detach()
             if self._consumers or (slot.stream != -1 and slot.stream != s.value):
                 self._order_reuse(s, slot.stream)
+        prev = slot.stream
         slot.stream = s.value
         po, pf, pr, pd, pfin, pinfo = slot.ptrs
-        if gated:  # validate_actions=True, device actions: the step is gated (st_gate_actions)
-            eng._gate_launch(a, s)
         try:
-            C.check(self._step_vec(eng._ctx, ctypes.c_void_p(a.data_ptr()), po, pf, pr, pd, pfin, pinfo, s))
-        except BaseException:
+            if gated:  # validate_actions=True, device actions: the step is gated (st_gate_actions)
+                eng._gate_launch(a, s)
+            try:
+                C.check(self._step_vec(eng._ctx, ctypes.c_void_p(a.data_ptr()), po, pf, pr, pd, pfin, pinfo, s))
+            except BaseException:
+                if gated:
+                    eng._gate_abort()
+                raise
             if gated:
-                eng._gate_abort()
+                eng._gate_wait()  # waits for the check only; raises KeyError if the step was skipped
+        except BaseException:
+            # a step that raised wrote nothing: copy=False's alternation stays
+            # where it was, so the next step takes this slot again and the last
+            # successful step's outputs keep their two steps
+            self._k, slot.stream = k0, prev
             raise
-        if gated:
-            eng._gate_wait()  # waits for the check only; raises KeyError if the step was skipped
         info = VecInfo(self, slot)
         if not self.copy:
             slot.owner = weakref.ref(info)

@@ -5,6 +5,7 @@
   before TetrisEngine.step changes anything) without draining the stream --
   a rejected step leaves every env exactly as it was, and the steps around
   it equal an unvalidated twin's;
+  (one gate block here; grids above one block: tests/test_gpu_gate_grid.py)
 * TetrisVecEnv copy=True slot reuse honours consumer streams
   (record_stream) and follows the caller's holding depth;
 * TetrisEnv's info['statistics'] is the env's one live shape-count dict
