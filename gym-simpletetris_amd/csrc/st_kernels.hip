@@ -197,10 +197,13 @@ constexpr int kRD = kNT;
 // step: K = 2,000 4.67-4.72 -> 4.64-4.67 us, profiles/r03/ab_step_lprio.txt).
 constexpr int kDrawPrio = 2;
 constexpr int kLogicPrio = 1;
+// (soff: a wave-uniform part of the offset, the instruction's scalar offset;
+// in range, off + soff lies within the resource; with off = kOff the access
+// is dropped whatever soff is)
 template <int AUX = 0>
-__device__ __forceinline__ void buf_store16(__amdgpu_buffer_rsrc_t r, uint32_t off, uint4 v) {
+__device__ __forceinline__ void buf_store16(__amdgpu_buffer_rsrc_t r, uint32_t off, uint4 v, uint32_t soff = 0u) {
     const i32x4 d = {(int)v.x, (int)v.y, (int)v.z, (int)v.w};
-    __builtin_amdgcn_raw_buffer_store_b128(d, r, off, 0, AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(d, r, off, soff, AUX);
 }
 
 __device__ __forceinline__ uint32_t &lcol(uint32_t *L, int x, int lane) {
@@ -218,11 +221,9 @@ __device__ __forceinline__ uint32_t &lcol(uint32_t *L, int x, int lane) {
 //    set bit of (column | floor) at or below it.  A column outside the board
 //    (legal only while its cells are above row 0) reads a wall and stops the
 //    piece as its lowest cell would enter row 0.
-__device__ __forceinline__ void read_cols(const uint32_t *L, int lane, uint32_t g, int x,
-                                          uint32_t (&v)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = L[(x + pc_dx(g, j) + kPad) * kWave + lane];
-}
+// (kTab descriptors: k_policy_greedy reads its columns itself and uses
+// drop_v; the step and rollout kernels use the box forms below, and
+// collides_v serves both -- byte j of m is column j's cells in either table)
 template <bool S32 = false>
 __device__ __forceinline__ bool collides_v(uint32_t m, int y, const uint32_t (&v)[4]) {
     uint32_t hit = 0;
@@ -243,7 +244,7 @@ __device__ __forceinline__ int drop_v(uint32_t g, int y, const uint32_t (&v)[4])
 }
 
 // _set_piece(True) (tetris_env.py:323-327): cells inside the board only,
-// as no-return LDS atomics.
+// as no-return LDS atomics (kTab descriptors: k_render).
 template <bool S32 = false>
 __device__ __forceinline__ void paint(uint32_t *L, int lane, uint32_t m, uint32_t g, int x, int y,
                                       uint32_t hmask) {
@@ -252,16 +253,10 @@ __device__ __forceinline__ void paint(uint32_t *L, int lane, uint32_t m, uint32_
         atomicOr(&L[(x + pc_dx(g, j) + kPad) * kWave + lane], pc_bits<S32>(m, j, y) & hmask);  // ds_or_b32
 }
 
-// _set_piece(False): erase the cells.
-template <bool S32 = false>
-__device__ __forceinline__ void erase(uint32_t *L, int lane, uint32_t m, uint32_t g, int x, int y,
-                                      uint32_t hmask) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        atomicAnd(&L[(x + pc_dx(g, j) + kPad) * kWave + lane], ~(pc_bits<S32>(m, j, y) & hmask));
-}
-
-// Box-column forms of read_cols / drop_v / paint / erase (kBox descriptors).
+// Box-column forms (kBox descriptors): the four columns from the box's
+// leftmost, one LDS address per descriptor.
+// paint_box = _set_piece(True), erase_box = _set_piece(False); a box column
+// without cells ORs 0 / ANDs ~0 into a board or wall column.
 // drop_box: q = the row below the column's lowest cell; a column without
 // cells has q = y - 64, so its shift is 0 and its distance ctz(column) + 64
 // - y exceeds every real column's (at most H + 2 - y: the floor bits stop a
@@ -1180,8 +1175,8 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
         // draw wave's path to B0
 #pragma unroll
         for (int i = 0; i < 28; ++i) {
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(tab_m) : "s"(kTab.m[i]), "i"(i));
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(tab_g) : "s"(kTab.g[i]), "i"(i));
+            asm("v_writelane_b32 %0, %1, %2" : "+v"(tab_m) : "s"(kBox.m[i]), "i"(i));
+            asm("v_writelane_b32 %0, %1, %2" : "+v"(tab_g) : "s"(kBox.g[i]), "i"(i));
         }
     }
     const int lrow = lane >> 4, lcc = 4 * (lane & 15);  // this lane's row-in-group, env slot
@@ -1288,8 +1283,8 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
         const uint2 cdesc = tab(id * 4 + cr);
         if constexpr (OVP && DO_L) pd_pv = tab(pv_id(mt0) * 4);
         uint32_t cur[4], cand[4];
-        read_cols(L, lane, desc.y, ax, cur);
-        read_cols(L, lane, cdesc.y, cx, cand);
+        read_box(L, lane, desc.y, ax, cur);
+        read_box(L, lane, cdesc.y, cx, cand);
         // branch-free: select the accepted position's descriptor and columns, then
         // one drop test (both arms would otherwise run in a divergent wave)
         const bool ok = tries && !collides_v<S32>(cdesc.x, ay, cand);
@@ -1299,7 +1294,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
         desc.y = ok ? cdesc.y : desc.y;
 #pragma unroll
         for (int j = 0; j < 4; ++j) cur[j] = ok ? cand[j] : cur[j];
-        int d = drop_v(desc.y, ay, cur);
+        int d = drop_box(desc.y, ay, cur);
         if (act == 2u) {                 // hard_drop :54-59
             ay += d;
             d = 0;
@@ -1329,11 +1324,12 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
         const auto rs = buf_rsrc(p.stats, (uint32_t)kHotRows * (uint32_t)sd * 4u);
         // (ablation 8192: from the first workgroup's lines -- their HBM reads gone, timing only)
         const uint32_t eo = (kAblate & 8192u) ? (uint32_t)lane * 4u : (uint32_t)e * 4u;
+        // (the row's offset is wave-uniform: the instruction's scalar offset,
+        // so one per-lane offset -- one select -- serves the five loads)
+        const uint32_t lo = locknow && !(kAblate & 2097152u) ? eo : kOff;  // (ablation 2097152: not loaded, timing only)
 #pragma unroll
-        for (int j = 0; j < 5; ++j)  // (ablation 2097152: not loaded, timing only)
-            lcv[j] = __builtin_amdgcn_raw_buffer_load_b32(
-                rs, locknow && !(kAblate & 2097152u) ? eo + (uint32_t)(ST_STAT_SCORE + j) * (uint32_t)sd * 4u : kOff,
-                0, 0);
+        for (int j = 0; j < 5; ++j)
+            lcv[j] = __builtin_amdgcn_raw_buffer_load_b32(rs, lo, (uint32_t)(ST_STAT_SCORE + j) * (uint32_t)sd * 4u, 0);
     }
     // the draw wave's next-generation chunk of this step: operands issued
     // before B1, so they arrive while it waits for the lock decision
@@ -1409,7 +1405,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
             height = o_height = (int32_t)ss(ST_STAT_PIECE_HEIGHT);
             deaths = o_deaths = (int32_t)ss(ST_STAT_DEATHS);
         }
-        paint<S32>(L, lane, desc.x, desc.y, ax, ay, hmask);
+        paint_box<S32>(L, lane, desc.x, desc.y, ax, ay, hmask);
         // Column words carry the floor bits, so the topmost cell of column v
         // is ctz(v) (H when empty) and its holes are H - ctz(v) - popc(v & hmask):
         // summed, holes = W*H - sum ctz(v) - (sum popc(v) - W*(32-H)).
@@ -1443,8 +1439,9 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
         }
         andv &= hmask;
         if constexpr (KSTEPS == 1) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bdirty |= 1u << (ax + pc_dx(desc.y, j));
+            // the columns holding the locked piece's cells: its box's first n
+            // (byte c of m is column c's cells, the empty ones last)
+            bdirty = (0xFu >> (__builtin_clz(desc.x) >> 3)) << box_x0(desc.y, ax);
             if (andv) bdirty = ~0u;
         }
         int32_t ncl = 0;
@@ -1562,7 +1559,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
         // terminal obs = L with its piece, :301).
         // Only rows (board columns x) that one of the lane's 4 envs changed are
         // written (buffer stores, see buf_rsrc).
-        if (died && !reset_now) erase<S32>(L, lane, desc.x, desc.y, ax, ay, hmask);
+        if (died && !reset_now) erase_box<S32>(L, lane, desc.x, desc.y, ax, ay, hmask);
         if (died) bdirty = ~0u;
         if constexpr (OVP) {
             // the overlay of every lane into its own plane: the current piece,
@@ -1578,9 +1575,13 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
             }
             const uint32_t om = spawn ? pd.x : desc.x, og = spawn ? pd.y : desc.y;
             const int ox = spawn ? W / 2 : ax, oy = spawn ? 0 : ay;
+            // (a box column without cells writes 0 into this lane's own word
+            // of a plane column that is zero already, or of a pad column,
+            // which nothing reads: the box lies within [-kPad, W + 3])
+            uint32_t *const ov0 = &sm.OV[(box_x0(og, ox) + kPad) * kWave + lane];
 #pragma unroll
             for (int j = 0; j < 4; ++j)  // (ablation 4194304: skipped, timing only)
-                if (!(kAblate & 4194304u)) sm.OV[(ox + pc_dx(og, j) + kPad) * kWave + lane] = pc_bits<S32>(om, j, oy) & hmask;
+                if (!(kAblate & 4194304u)) ov0[j * kWave] = pc_bits<S32>(om, j, oy) & hmask;
         }
         uint4 km, bd4;
         uint4 bw[NBQ], ow[NBQ];
@@ -1660,7 +1661,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
                 v.w &= km.w;
                 // row 4q + lrow; padding rows (>= W) are never dirty
                 const bool dirty = ((bdl >> (4 * q)) & 1u) && 4 * q + lrow < W && !(kAblate & 4096u);
-                buf_store16<kST>(rb, dirty ? boff + (uint32_t)(4 * q) * (uint32_t)sd * 4u : kOff, v);
+                buf_store16<kST>(rb, dirty ? boff : kOff, v, (uint32_t)(4 * q) * (uint32_t)sd * 4u);
             }
         }
         // (below: the ragged / unaligned obs path and the float32 writer read
@@ -1824,9 +1825,10 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
             // where a row did not change
             const auto rs = buf_rsrc(p.stats, (uint32_t)kHotRows * (uint32_t)sd * 4u);
             const uint32_t eo = (uint32_t)e * 4u;
+            // (the row's offset as the store's scalar offset: no per-lane add)
             auto put = [&](int r, int32_t v, bool on) {
-                __builtin_amdgcn_raw_buffer_store_b32((uint32_t)v, rs, on ? eo + (uint32_t)r * (uint32_t)sd * 4u : kOff,
-                                                      0, kST);
+                __builtin_amdgcn_raw_buffer_store_b32((uint32_t)v, rs, on ? eo : kOff, (uint32_t)r * (uint32_t)sd * 4u,
+                                                      kST);
             };
             put(ST_STAT_TIME, time, true);
             put(kPieceRow, (int32_t)pw_out, true);
@@ -1872,7 +1874,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
 
         // ---- observation (tetris_env.py:301-302): board + current piece ----
         if constexpr (KSTEPS != 1) {
-            if (KSTEPS != 1 || spawn) paint<S32>(L, lane, odesc.x, odesc.y, oax, oay, hmask);
+            if (KSTEPS != 1 || spawn) paint_box<S32>(L, lane, odesc.x, odesc.y, oax, oay, hmask);
         }
         wave_sync();
         const bool wide_obs = (p.n & 3) == 0 && e0 + kWave <= p.n &&
@@ -2006,7 +2008,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
             // lane: non-locking lanes and spawns (overlay cells were empty), and a
             // death without auto-reset (R8: _set_piece(False), tetris_env.py:303).
             wave_sync();
-            erase<S32>(L, lane, odesc.x, odesc.y, oax, oay, hmask);
+            erase_box<S32>(L, lane, odesc.x, odesc.y, oax, oay, hmask);
             if (reset_now)
                 for (int x = 0; x < W; ++x) lcol(L, x, lane) = floorb;
         }
