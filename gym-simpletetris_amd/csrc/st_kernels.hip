@@ -31,71 +31,15 @@ constexpr int kShapes[7][4][2] = {
     {{0, 0}, {0, -1}, {-1, 0}, {-1, -1}},
 };
 
-// One descriptor per (piece, rot) = {m, g}, four column records each:
-//   m: byte j = the column's cells as a bit mask biased by 3 (bit dy+3);
-//   g: 6 bits per column j: dx+3 (bits 6j..6j+2), bottom dy+3 (6j+3..6j+5).
-// Tetromino columns are vertically contiguous runs (checked below); pieces
-// with fewer than 4 columns repeat their last column (OR/AND/min idempotent).
-// rot r = r applications of rotated(cclk=False) (tetris_env.py:22-26).
+// One descriptor per (piece, rot) = {m, g}; rot r = r applications of
+// rotated(cclk=False) (tetris_env.py:22-26).  Tetromino columns are
+// vertically contiguous runs (checked below).
 struct PieceTab {
     uint32_t m[28], g[28];
     bool ok;
 };
 
-constexpr PieceTab make_piece_tab() {
-    PieceTab t{};
-    t.ok = true;
-    for (int p = 0; p < 7; ++p) {
-        int cx[4] = {}, cy[4] = {};
-        for (int c = 0; c < 4; ++c) {
-            cx[c] = kShapes[p][c][0];
-            cy[c] = kShapes[p][c][1];
-        }
-        for (int r = 0; r < 4; ++r) {
-            uint32_t m = 0, g = 0, lm = 0, lg = 0;
-            int ncol = 0;
-            for (int dx = -3; dx <= 3; ++dx) {
-                int ymin = 99, ymax = -99, cnt = 0;
-                uint32_t bits = 0;
-                for (int c = 0; c < 4; ++c)
-                    if (cx[c] == dx) {
-                        ++cnt;
-                        ymin = cy[c] < ymin ? cy[c] : ymin;
-                        ymax = cy[c] > ymax ? cy[c] : ymax;
-                        bits |= 1u << (cy[c] + 3);
-                    }
-                if (!cnt) continue;
-                if (cnt != ymax - ymin + 1 || ymin < -3 || ymax > 3) t.ok = false;
-                lm = bits;
-                lg = (uint32_t)(dx + 3) | ((uint32_t)(ymax + 3) << 3);
-                m |= lm << (8 * ncol);
-                g |= lg << (6 * ncol);
-                ++ncol;
-            }
-            for (int j = ncol; j < 4; ++j) {
-                m |= lm << (8 * j);
-                g |= lg << (6 * j);
-            }
-            t.m[p * 4 + r] = m;
-            t.g[p * 4 + r] = g;
-            for (int c = 0; c < 4; ++c) {  // rotated(cclk=False): (i, j) -> (j, -i)
-                const int i = cx[c], j = cy[c];
-                cx[c] = j;
-                cy[c] = -i;
-            }
-        }
-    }
-    return t;
-}
-constexpr PieceTab kTab = make_piece_tab();
-static_assert(kTab.ok, "every tetromino column must be a contiguous run within [-3, 3]");
-#define ST_TAB28(a) {a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], \
-                     a[12], a[13], a[14], a[15], a[16], a[17], a[18], a[19], a[20], a[21], a[22], \
-                     a[23], a[24], a[25], a[26], a[27]}
-__constant__ uint32_t c_tab_m[28] = ST_TAB28(kTab.m);
-__constant__ uint32_t c_tab_g[28] = ST_TAB28(kTab.g);
-
-// The rollout's piece table ("box columns"): a rotation's columns as four
+// The piece table ("box columns"): a rotation's columns as four
 // consecutive board columns from its leftmost, dx0 = (g & 7) - 3 (at most 0:
 // every shape holds its anchor cell), column c's cells in byte c of m (0:
 // none) and, in bits [3 + 7c, 10 + 7c) of g as a signed field, the row
@@ -149,12 +93,16 @@ constexpr PieceTab make_box_tab() {
 }
 constexpr PieceTab kBox = make_box_tab();
 static_assert(kBox.ok, "every rotation must span at most four columns from dx0 in [-3, 0]");
+#define ST_TAB28(a) {a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], a[11], \
+                     a[12], a[13], a[14], a[15], a[16], a[17], a[18], a[19], a[20], a[21], a[22], \
+                     a[23], a[24], a[25], a[26], a[27]}
+// (k_render, k_policy_greedy; the step and rollout kernels build the table from immediates)
+__constant__ uint32_t c_tab_m[28] = ST_TAB28(kBox.m);
+__constant__ uint32_t c_tab_g[28] = ST_TAB28(kBox.g);
 
-// Column j of a descriptor: dx, bottom dy, and its cells at anchor row y as
-// board-row bits; cells with y < 0 vanish (is_occupied skips them,
-// tetris_env.py:32-33; _set_piece clips them, :326).
-__device__ __forceinline__ int pc_dx(uint32_t g, int j) { return (int)((g >> (6 * j)) & 7u) - 3; }
-__device__ __forceinline__ int pc_bot(uint32_t g, int j) { return (int)((g >> (6 * j + 3)) & 7u) - 3; }
+// Column j of a descriptor: its cells at anchor row y as board-row bits;
+// cells with y < 0 vanish (is_occupied skips them, tetris_env.py:32-33;
+// _set_piece clips them, :326).
 // S32: board height <= 25 (compile time), so a cell's bit (row + 3 <= 30)
 // fits a 32-bit shift.  (The 64-bit form's don't-care high half can land in
 // a register still waiting on a load -- measured: the lock path's paint
@@ -210,20 +158,11 @@ __device__ __forceinline__ uint32_t &lcol(uint32_t *L, int x, int lane) {
     return L[(x + kPad) * kWave + lane];
 }
 
-// The four column words a descriptor touches at anchor column x (issued as
-// one batch of LDS reads), and the collision / drop tests on them:
+// The collision test on the four column words a descriptor touches (read_box
+// below issues them as one batch of LDS reads):
 //  collides_v = is_occupied (tetris_env.py:29-36) with the floor bits and the
 //    all-ones wall columns standing in for the bounds checks; cells with y < 0
-//    vanish in pc_bits (R2);
-//  drop_v = the number of free soft_drops below a legal position, i.e.
-//    hard_drop's loop count (tetris_env.py:54-59): only each column's lowest
-//    cell can meet an obstacle first, and the first obstacle row is the lowest
-//    set bit of (column | floor) at or below it.  A column outside the board
-//    (legal only while its cells are above row 0) reads a wall and stops the
-//    piece as its lowest cell would enter row 0.
-// (kTab descriptors: k_policy_greedy reads its columns itself and uses
-// drop_v; the step and rollout kernels use the box forms below, and
-// collides_v serves both -- byte j of m is column j's cells in either table)
+//    vanish in pc_bits (R2).
 template <bool S32 = false>
 __device__ __forceinline__ bool collides_v(uint32_t m, int y, const uint32_t (&v)[4]) {
     uint32_t hit = 0;
@@ -231,33 +170,17 @@ __device__ __forceinline__ bool collides_v(uint32_t m, int y, const uint32_t (&v
     for (int j = 0; j < 4; ++j) hit |= pc_bits<S32>(m, j, y) & v[j];
     return hit != 0;
 }
-__device__ __forceinline__ int drop_v(uint32_t g, int y, const uint32_t (&v)[4]) {
-    int dist = 1 << 20;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int yb = y + pc_bot(g, j);
-        const int s = yb + 1 > 0 ? yb + 1 : 0;
-        const int k = __builtin_ctz(v[j] & (~0u << s)) - yb - 1;
-        dist = k < dist ? k : dist;
-    }
-    return dist;
-}
 
-// _set_piece(True) (tetris_env.py:323-327): cells inside the board only,
-// as no-return LDS atomics (kTab descriptors: k_render).
-template <bool S32 = false>
-__device__ __forceinline__ void paint(uint32_t *L, int lane, uint32_t m, uint32_t g, int x, int y,
-                                      uint32_t hmask) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        atomicOr(&L[(x + pc_dx(g, j) + kPad) * kWave + lane], pc_bits<S32>(m, j, y) & hmask);  // ds_or_b32
-}
-
-// Box-column forms (kBox descriptors): the four columns from the box's
-// leftmost, one LDS address per descriptor.
-// paint_box = _set_piece(True), erase_box = _set_piece(False); a box column
+// The four columns from the box's leftmost, one LDS address per descriptor.
+// paint_box = _set_piece(True) (tetris_env.py:323-327: cells inside the board
+// only, as no-return LDS atomics), erase_box = _set_piece(False); a box column
 // without cells ORs 0 / ANDs ~0 into a board or wall column.
-// drop_box: q = the row below the column's lowest cell; a column without
+// drop_box = the number of free soft_drops below a legal position, i.e.
+// hard_drop's loop count (tetris_env.py:54-59): only each column's lowest
+// cell can meet an obstacle first, and the first obstacle row is the lowest
+// set bit of (column | floor) at or below it.  A column outside the board
+// (legal only while its cells are above row 0) reads a wall and stops the
+// piece as its lowest cell would enter row 0.  q = the row below the column's lowest cell; a column without
 // cells has q = y - 64, so its shift is 0 and its distance ctz(column) + 64
 // - y exceeds every real column's (at most H + 2 - y: the floor bits stop a
 // drop by row H < 32; every column word holds floor or wall bits, so ctz
@@ -304,6 +227,251 @@ __device__ __forceinline__ uint32_t compact(uint32_t v, uint32_t full) {
         v = (v & ~(above | (1u << r))) | ((v & above) << 1);
     }
     return v;
+}
+
+// ---------------------------------------------------------------- step rules
+// TetrisEngine.step's rules (tetris_env.py:245-299), one copy for the logic
+// waves of k_step, k_rollout2 (step_logic) and k_rollout (rollout_wave) --
+// but for the scoring part, which step_logic keeps inline (see lock_score).
+// Arrays go by reference to sized arrays (through a pointer they would be
+// left in scratch memory).
+
+// (x + 1) % lock_mod for l1 = x + 1 >= 1 (tetris_env.py:175): l1 <= lock_mod
+// except after a host-written state (a lock field up to 2^15), which a
+// division reduces -- only in a wave where some lane needs it (wave-uniform
+// branch: a bounded cost once per host write, not a subtraction loop of up to
+// 2^15 rounds; as a plain % the division ran, exec-masked, on every step)
+__device__ __forceinline__ int lock_next(int l1, int lock_mod) {
+    int r = l1 < lock_mod ? l1 : l1 - lock_mod;
+    if (__ballot(r >= lock_mod)) r = r >= lock_mod ? r % lock_mod : r;
+    return r;
+}
+
+// The move, first half: the candidate position of the action
+// (tetris_env.py:245; value_action_map :152-160).  The caller reads the
+// current and the candidate descriptor's columns (read_box) in one LDS round
+// trip; the collision and drop tests of move_resolve are then pure VALU.
+struct MoveCand {
+    bool tries;
+    int cx, cr;
+};
+__device__ __forceinline__ MoveCand move_cand(uint32_t act, int ax, int rot) {
+    MoveCand mc;
+    mc.tries = act == 0u || act == 1u || act == 4u || act == 5u;
+    mc.cx = ax + (act == 0u ? -1 : (act == 1u ? 1 : 0));
+    mc.cr = (rot + (act == 4u ? 1 : 0) + (act == 5u ? 3 : 0)) & 3;  // (selects: the ternary chain became an exec-mask branch)
+    return mc;
+}
+// The move, second half: accept or keep, drop, gravity and lock delay
+// (tetris_env.py:245-262).  Returns whether the piece locks in this step.
+template <bool S32>
+__device__ __forceinline__ bool move_resolve(uint32_t act, const MoveCand &mc, uint2 cdesc, const uint32_t (&cand)[4],
+                                             uint2 &desc, uint32_t (&cur)[4], int &rot, int &ax, int &ay, int &lock,
+                                             int32_t &time, int32_t &rew, uint32_t kFlags, uint32_t kAblate,
+                                             int lock_mod) {
+    // branch-free: select the accepted position's descriptor and columns, then
+    // one drop test (both arms would otherwise run in a divergent wave)
+    const bool ok = mc.tries && !collides_v<S32>(cdesc.x, ay, cand);
+    ax = ok ? mc.cx : ax;
+    rot = ok ? mc.cr : rot;
+    desc.x = ok ? cdesc.x : desc.x;
+    desc.y = ok ? cdesc.y : desc.y;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) cur[j] = ok ? cand[j] : cur[j];
+    int d = drop_box(desc.y, ay, cur);
+    if (act == 2u) {                 // hard_drop :54-59
+        ay += d;
+        d = 0;
+    } else if (act == 3u && d > 0) { // soft_drop :49-51
+        ay += 1;
+        d -= 1;
+    }
+    // ---- gravity + lock delay (tetris_env.py:247-262) ----
+    if (d > 0) {
+        ay += 1;
+        d -= 1;
+        if (kFlags & ST_STEP_RESET) lock = 0;
+    }
+    time += 1;
+    rew = (kFlags & ST_REWARD_STEP) ? 1 : 0;
+    bool locknow = false;
+    if (d == 0) {
+        const int l1 = lock + 1;  // (x + 1) % lock_mod; x < lock_mod unless set_state said otherwise
+        lock = lock_next(l1, lock_mod);
+        locknow = lock == 0 && !(kAblate & 1u);
+    }
+    return locknow;
+}
+
+// The board part of a lock (tetris_env.py:263-265, _clear_lines :205-216):
+// the piece painted, full rows found and compacted.
+// Column words carry the floor bits, so the topmost cell of column v
+// is ctz(v) (H when empty) and its holes are H - ctz(v) - popc(v & hmask):
+// summed, holes = W*H - sum ctz(v) - (sum popc(v) - W*(32-H)).
+__device__ __forceinline__ int32_t holes_of(uint32_t sctz, uint32_t spop, int W, int H) {  // _count_holes :218-220
+    return W * H - (int32_t)sctz - ((int32_t)spop - W * (32 - H));
+}
+template <int N>
+__device__ __forceinline__ void hole_sums(const uint32_t (&v)[N], uint32_t &sctz, uint32_t &spop) {
+    uint32_t hc = 0, hp = 0;
+#pragma unroll
+    for (int x = 0; x < N; ++x) {
+        hc += __builtin_ctz(v[x]);
+        hp += __builtin_popcount(v[x]);
+    }
+    sctz = hc;
+    spop = hp;
+}
+template <int WT>
+struct LockCols {
+    int32_t ncl;               // full rows cleared
+    uint32_t orv;              // the OR of the columns after the lock (board rows only)
+    uint32_t sctz, spop;       // the hole sums after the lock (EAGERH, or after hole_sums(cw, ...))
+    uint32_t cw[WT ? WT : 1];  // compile-time width: the column words after the lock
+};
+// EAGERH: the hole sums are accumulated with the row tests; otherwise the
+// caller counts them from cw where it reads holes (compile-time width only).
+template <int WT, bool S32, bool EAGERH>
+__device__ __forceinline__ void lock_board(uint32_t *L, int lane, int W, uint32_t hmask, uint32_t floorb, uint2 desc,
+                                           int ax, int ay, LockCols<WT> &r) {
+    static_assert(EAGERH || WT != 0, "a recount needs the column words");
+    paint_box<S32>(L, lane, desc.x, desc.y, ax, ay, hmask);
+    uint32_t andv = ~0u, orv = 0, sctz = 0, spop = 0;
+    // (compile-time width: all W column reads issued before any is used,
+    // one LDS round trip -- left to itself the scheduler reused the first
+    // reads' registers as accumulators and issued the last pair after
+    // waiting for the others; the clear path reuses the words)
+    if constexpr (WT != 0) {
+#pragma unroll
+        for (int x = 0; x < WT; ++x) r.cw[x] = lcol(L, x, lane);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int x = 0; x < WT; ++x) {
+            const uint32_t v = r.cw[x];
+            andv &= v;
+            orv |= v;
+            if constexpr (EAGERH) {
+                sctz += __builtin_ctz(v);
+                spop += __builtin_popcount(v);
+            }
+        }
+    } else {
+#pragma unroll 8
+        for (int x = 0; x < W; ++x) {
+            const uint32_t v = lcol(L, x, lane);
+            andv &= v;
+            orv |= v;
+            sctz += __builtin_ctz(v);
+            spop += __builtin_popcount(v);
+        }
+    }
+    andv &= hmask;
+    int32_t ncl = 0;
+    if (andv) {  // full rows: compact, recount
+        ncl = __builtin_popcount(andv);
+        orv = 0;
+        sctz = spop = 0;
+        if constexpr (WT != 0) {
+            // the columns in registers, one full row per round for all of
+            // them (compact()'s steps in the same order): the rounds are
+            // the wave's largest clear count, not one loop per column
+            uint32_t c[WT];
+#pragma unroll
+            for (int x = 0; x < WT; ++x) c[x] = r.cw[x] & hmask;
+            uint32_t full = andv;
+            while (full) {
+                const int rr = __builtin_ctz(full);
+                full &= full - 1u;
+                const uint32_t above = (1u << rr) - 1u;
+                const uint32_t keep = ~(above | (1u << rr));
+#pragma unroll
+                for (int x = 0; x < WT; ++x) c[x] = (c[x] & keep) | ((c[x] & above) << 1);
+            }
+#pragma unroll
+            for (int x = 0; x < WT; ++x) {
+                const uint32_t v = c[x] | floorb;
+                r.cw[x] = v;
+                lcol(L, x, lane) = v;
+                orv |= v;
+                if constexpr (EAGERH) {
+                    sctz += __builtin_ctz(v);
+                    spop += __builtin_popcount(v);
+                }
+            }
+        } else {
+#pragma unroll 8
+            for (int x = 0; x < W; ++x) {
+                const uint32_t v = compact(lcol(L, x, lane) & hmask, andv) | floorb;
+                lcol(L, x, lane) = v;
+                orv |= v;
+                sctz += __builtin_ctz(v);
+                spop += __builtin_popcount(v);
+            }
+        }
+    }
+    r.ncl = ncl;
+    r.orv = orv & hmask;
+    r.sctz = sctz;
+    r.spop = spop;
+}
+
+// The scoring part of a lock (tetris_env.py:264-299): the cleared lines'
+// score, death, the height and holes penalties, spawn.  The counters go by
+// reference; the old holes and height by value (st_step's are loaded late,
+// the others sit in registers).  count_holes() is called where the rules
+// read the new hole count: LAZYH, only at a death or under a holes flag
+// (hlazy: not counted, the caller recounts where it reads holes next).
+// (k_rollout's copy; step_logic -- k_step and k_rollout2 -- keeps these rules
+// inline for a measured reason, see there.)
+struct LockRes {
+    bool died, spawn;
+    bool hset;   // height was set
+    bool hlazy;  // LAZYH: holes was not counted
+};
+template <bool LAZYH, class HF>
+__device__ __forceinline__ LockRes lock_score(uint32_t kFlags, int32_t ncl, uint32_t orv, HF &&count_holes,
+                                              int32_t old_holes, int32_t old_height, int32_t &rew, int32_t &score,
+                                              int32_t &lines, int32_t &holes, int32_t &height, int32_t &deaths) {
+    LockRes res = {false, false, false, false};
+    lines += ncl;
+    if (kFlags & ST_ADVANCED_CLEARS) {  // :266-269, 2.5 * [0,40,100,300,1200]
+        // [0, 40, 100, 300, 1200][ncl] as 12-bit fields of one constant
+        // (ncl > 4 only from a crafted set_state board: 0, as before)
+        constexpr uint64_t kClr = (40ull << 12) | (100ull << 24) | (300ull << 36) | (1200ull << 48);
+        const int32_t sc = ncl <= 4 ? (int32_t)((kClr >> (12 * ncl)) & 0xFFFu) : 0;
+        rew += (sc * 5) / 2;
+        score += sc;
+    } else if (kFlags & ST_HIGH_SCORING) {  // :270-272
+        rew += 1000 * ncl;
+        score += ncl;
+    } else {  // :273-275
+        rew += 100 * ncl;
+        score += ncl;
+    }
+    if (orv & 1u) {  // death :277-281
+        holes = count_holes();
+        deaths += 1;
+        res.died = true;
+        rew = -100;
+    } else {  // :283-299
+        // LAZYH: holes feeds the reward only under the two holes flags;
+        // otherwise it is recounted from the board where it is
+        // read next (a death, the epilogue)
+        if (!LAZYH || (kFlags & (ST_PENALISE_HOLES | ST_PENALISE_HOLES_INCREASE))) holes = count_holes();
+        else res.hlazy = true;
+        const int32_t hgt = __builtin_popcount(orv);  // sum(np.any(board, axis=0))
+        if (kFlags & ST_PENALISE_HEIGHT) {
+            rew -= hgt;
+        } else if (kFlags & ST_PENALISE_HEIGHT_INCREASE) {
+            if (hgt > old_height) rew -= 10 * (hgt - old_height);
+            height = hgt;
+            res.hset = true;
+        }
+        if (kFlags & ST_PENALISE_HOLES) rew -= 5 * holes;
+        else if (kFlags & ST_PENALISE_HOLES_INCREASE) rew -= 5 * (holes - old_holes);
+        res.spawn = true;
+    }
+    return res;
 }
 
 // Every kernel below that exchanges data between lanes through LDS runs one
@@ -386,7 +554,7 @@ __device__ __forceinline__ uint32_t mt_pack(int idx, int pg, int cur) {
     return (uint32_t)idx | ((uint32_t)pg << 10) | ((uint32_t)cur << 20);
 }
 // The preview (the piece the env's NEXT spawn takes, drawn one spawn ahead so
-// that no step waits on a draw; see run_steps) in the upper bits of the same
+// that no step waits on a draw; see step_draw) in the upper bits of the same
 // word: pv << 21 | ok << 24 | c << 25, c = the MT words its draw
 // consumed (6 bits; a draw of > 62 words has p < 2^-62), so the reference's
 // state -- the one before the preview was drawn -- is c words back
@@ -857,16 +1025,6 @@ __device__ __forceinline__ int win_lim(uint32_t m) {
     return l < kMtWin ? l : kMtWin;
 }
 
-// (x + 1) % lock_mod for l1 = x + 1 >= 1 (tetris_env.py:175): l1 <= lock_mod
-// except after a host-written state (a lock field up to 2^15), which a
-// division reduces -- only in a wave where some lane needs it (wave-uniform
-// branch: a bounded cost once per host write, not a subtraction loop of up to
-// 2^15 rounds; as a plain % the division ran, exec-masked, on every step)
-__device__ __forceinline__ int lock_next(int l1, int lock_mod) {
-    int r = l1 < lock_mod ? l1 : l1 - lock_mod;
-    if (__ballot(r >= lock_mod)) r = r >= lock_mod ? r % lock_mod : r;
-    return r;
-}
 __device__ __forceinline__ uint32_t pack_piece(int id, int rot, int ax, int ay, int lock) {
     return (uint32_t)id | ((uint32_t)rot << 3) | ((uint32_t)ax << 5) | ((uint32_t)ay << 11) |
            ((uint32_t)lock << 17);
@@ -913,7 +1071,7 @@ struct StepLds {
     float F4[F32 ? 64 : 4] __attribute__((aligned(16)));
     // st_step: the obs overlay plane, laid out like L
     uint32_t OV[KSTEPS == 1 ? kCols * kWave : 4] __attribute__((aligned(16)));
-    // two-wave st_step hand-offs (see run_steps)
+    // two-wave st_step hand-offs (see step_logic / step_draw)
     uint32_t dump[kWave] __attribute__((aligned(16)));  // the logic wave's padding-row writes
     // (step-parity double buffers where a wave may write step t+1's value
     // before the other has read step t's)
@@ -923,7 +1081,8 @@ struct StepLds {
     uint32_t f1, f2;  // = t + 1 once step t's draw mask / first picks are written
 };
 
-// Roles of run_steps.  st_step runs TWO waves per 64 envs: the logic wave
+// The two waves of a step kernel (step_logic and step_draw, below).  st_step
+// runs TWO waves per 64 envs: the logic wave
 // (action, lock path, board / obs / counter outputs) and the draw wave (MT
 // words, the next-generation block, the piece draw), so the draw no longer
 // sits on the logic wave's chain.  That works because spawns take a piece
@@ -933,9 +1092,7 @@ struct StepLds {
 // (every spawn / reset still consumes the next draw, with the shape counts of
 // that moment: the preview is drawn right after the previous spawn's count
 // update, and counts change only at spawns); st_mt_sync rewinds the preview's
-// words for the host.  k_rollout2 (KSTEPS == 0) runs the same two roles.
-constexpr int kRoleL = 1;
-constexpr int kRoleD = 2;
+// words for the host.  k_rollout2 (KSTEPS == 0) runs the same two waves.
 
 __device__ __forceinline__ void wg_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1009,251 +1166,405 @@ __device__ __forceinline__ void lds_flag_wait_ge(uint32_t *f, uint32_t v) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-// ROLE = kRoleL / kRoleD: the logic or the draw wave of a workgroup.
-// KSTEPS == 1: TetrisEngine.step once (st_step); KSTEPS == 0: p.k consecutive
-// steps (k_rollout2, st_rollout above 4 workgroups per CU) with the board and
-// counters kept in LDS between steps, actions read one step ahead, and
-// per-step outputs at [t].  State is
-// loaded once at the start and stored once at the end.
+// ---- what the waves of the step and rollout kernels share ----
+// timing ablations (tools/ablate.sh) exist only in -DST_ABLATION=1 builds:
+// as runtime flags each costs two SGPRs of lane masks, and the rollout
+// loop is at the SGPR limit
+__device__ __forceinline__ uint32_t ablate_bits([[maybe_unused]] const KParams &p) {
+#if defined(ST_ABLATION) && ST_ABLATION
+    return p.ablate;
+#else
+    return 0u;
+#endif
+}
 // SC0: the context has no scoring flags (the reference's defaults,
 // tetris_env.py:126-137): those tests fold away at compile time (measured:
 // the rollout loop otherwise holds each flag as a 64-bit lane mask at the
 // SGPR limit, -5% packed rollout; st_step -1%).
-// VEC (st_step_vec): the vector env's outputs -- with
-// p.final_obs, an env reset in this step returns the reset obs (the empty
-// board clear() returns, tetris_env.py:306-315, :405-411) and its terminal
-// obs goes to final_obs; with p.info, every counter row after the step is
-// written to info [ST_NSTAT][n] (the ep_* rows: the finished episode's where
-// the env was reset, else 0).
-template <int WT, int HT, bool F32, bool STAMP, int KSTEPS, bool SC0, int ROLE, bool VEC = false>
-__device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KSTEPS> &sm) {
-    static_assert(ROLE == kRoleL || ROLE == kRoleD, "run_steps: the logic or the draw wave");
-    static_assert(!VEC || KSTEPS == 1, "VEC: st_step only");
-    constexpr bool DO_L = ROLE == kRoleL;  // action, lock path, outputs
-    constexpr bool DO_D = ROLE == kRoleD;  // MT words, next-generation block, draws
-    [[maybe_unused]] uint64_t tstamp[12] = {};
-    [[maybe_unused]] uint32_t tacc[12] = {};  // rollout stamp build: per-phase cycle totals
-    [[maybe_unused]] uint64_t tlast = 0;
-    [[maybe_unused]] uint64_t draw_kind = 0;  // stamp build: 1 = a lane twisted, 2 = a draw ran past 8 words
-    constexpr bool S32 = HT != 0 && HT <= 25;  // see pc_bits
-    const uint32_t kFlags = SC0 ? (p.flags & (ST_REWARD_STEP | ST_STEP_RESET)) : p.flags;
+template <bool SC0>
+__device__ __forceinline__ uint32_t step_flags(const KParams &p) {
+    return SC0 ? (p.flags & (ST_REWARD_STEP | ST_STEP_RESET)) : p.flags;
+}
 
-    // timing ablations (tools/ablate.sh) exist only in -DST_ABLATION=1 builds:
-    // as runtime flags each costs two SGPRs of lane masks, and the rollout
-    // loop is at the SGPR limit
-#if defined(ST_ABLATION) && ST_ABLATION
-    const uint32_t kAblate = p.ablate;
-#else
-    constexpr uint32_t kAblate = 0u;
-#endif
-    [[maybe_unused]] uint64_t rt0 = 0;
-    if constexpr (STAMP) {
-        rt0 = __builtin_amdgcn_s_memrealtime();
-        tlast = __builtin_amdgcn_s_memtime();
-    }
-    ST_STAMP(0);
-    if constexpr (ROLE == kRoleL && KSTEPS == 1) __builtin_amdgcn_s_setprio(kLogicPrio);
-    uint32_t *const L = sm.L;
-    uint32_t *const SS = sm.SS;
-    const int W = WT ? WT : p.W;
-    const int H = HT ? HT : p.H;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t e0 = (int64_t)blockIdx.x * kWave;
-    const int64_t e = e0 + lane;
-    const int64_t sd = p.stride;
-    const bool real = e < p.n;
-    const uint32_t hmask = (1u << H) - 1u;
-    const uint32_t floorb = ~hmask;
-
-    // ---- loads: 16 B per lane (a wave's slice of one SoA row is 256 B) ----
-    // Lane l covers row 4q + l/16, envs 4(l%16)..+3: one per-lane 32-bit offset
-    // `loff` serves every 4-row group q (the group's base is wave-uniform), so
-    // addresses are SGPR base + VGPR offset.  The board allocation is padded
-    // to a multiple of 4 rows; rows >= W land in the right-wall LDS columns,
-    // which are written after them.  Counter rows: 0..14 plus row 15 (unused).
-    // Two waves: the logic wave loads the board and counter groups 0-1
-    // (time .. count1), the draw wave groups 2-3 (count2 .. MT word, piece).
-    const uint32_t loff = (uint32_t)(lane >> 4) * (uint32_t)sd + 4u * (uint32_t)(lane & 15);
-    constexpr int NBQ = ((WT ? WT : kMaxW) + 3) / 4;  // board 4-row groups
-    const uint32_t *bsrc = p.board + e0;
-    // (ablation 1024: every wave's counter groups from the first workgroup's
-    // lines -- the counter rows' HBM reads gone, timing only)
-    const uint32_t *ssrc = reinterpret_cast<const uint32_t *>(p.stats) + ((kAblate & 1024u) ? 0 : e0);
-    constexpr bool OVP = KSTEPS == 1;
-    // st_step (not st_step_vec, whose info snapshot needs every counter of
-    // every env): LATE COUNTERS.  The prologue's load burst carries only what
-    // every env needs at the step start -- board, action, time, piece word,
-    // MT word -- and the lock-only counter rows are read per locking lane
-    // once the lock decision is known (logic: score .. deaths, issued before
-    // B1, needed at the end of the lock path; draw: the shape counts, issued
-    // with the MT window after B1)
-    // (round 4, profiles/r04/ab_late_counters.txt: K = 2,000 4.642-4.643 ->
-    // 4.605-4.635 us; reading the draw wave's shape counts late as well was
-    // +6% -- its post-B1 chain, window + counts + draw parameters, became the
-    // step's -- and was dropped)
-    constexpr bool LCL = KSTEPS == 1 && !VEC;
-    // staged counter groups (rows 4q .. 4q + 3): logic 0-1, draw 2-3; with
-    // late rows only what the other role still reads early
-    // LCL: the draw wave stages exactly the rows it reads, the shape counts
-    // and the MT word (rows COUNT0 .. MT_INDEX: two 4-row groups from row 6,
-    // a group's base row needs no alignment) -- round 4 staged rows 4..15,
-    // 16 B per env more
-    static_assert(ST_STAT_MT_INDEX == ST_STAT_COUNT0 + 7, "counts and MT word: 8 consecutive rows");
-    auto mine_q = [&](int q) {
-        if constexpr (LCL) return ROLE == kRoleD && (q == 1 || q == 2);
-        return (ROLE == kRoleL) == (q < 2);
-    };
-    auto qbase = [&](int q) -> int {  // first stats row of staged group q
-        if constexpr (LCL) return ST_STAT_COUNT0 + 4 * (q - 1);
-        return 4 * q;
-    };
+// A wave's view of its 64 envs and of the workgroup's LDS (StepLds or RoLds:
+// the same member names): lane and env indices, the staged counter rows and
+// the piece table.
+// Loads and stores move 16 B per lane (a wave's slice of one SoA row is
+// 256 B): lane l covers row 4q + l/16 (lrow), envs 4(l%16)..+3 (lcc): one
+// per-lane 32-bit offset `loff` serves every 4-row group q (the group's base
+// is wave-uniform), so addresses are SGPR base + VGPR offset.
+// (W, H, hmask and floorb stay locals of the wave functions: for a fixed
+// board size they are constant expressions there, folded into the index
+// arithmetic before any optimisation; as members they fold late, into a
+// different instruction stream.)
+struct WaveCtx {
+    int lane;
+    int64_t e0, e, sd;
+    bool real;
+    uint32_t loff;
+    int lrow, lcc;  // this lane's row-in-group, env slot
+    uint32_t *SS;
+    const uint32_t *T2;
+    template <class LDS>
+    __device__ __forceinline__ WaveCtx(const KParams &p, LDS &sm)
+        : lane(threadIdx.x & (kWave - 1)), e0((int64_t)blockIdx.x * kWave), e(e0 + lane), sd(p.stride), real(e < p.n),
+          loff((uint32_t)(lane >> 4) * (uint32_t)sd + 4u * (uint32_t)(lane & 15)), lrow(lane >> 4),
+          lcc(4 * (lane & 15)), SS(sm.SS), T2(sm.T2) {}
     // Rows past the last real row (board padding, counter row 15) re-read the
     // last row -- the same cache line another lane fetches -- instead of
     // fetching padding; the loads stay unconditional (a load under a branch
     // costs a full vmcnt wait at the join).
-    auto clamp_off = [&](int q, int nrows) -> uint32_t {
+    __device__ __forceinline__ uint32_t clamp_off(int q, int nrows) const {
         const int r = 4 * q + (lane >> 4) < nrows ? (lane >> 4) : nrows - 1 - 4 * q;
         return (uint32_t)r * (uint32_t)sd + 4u * (uint32_t)(lane & 15);
-    };
+    }
+    __device__ __forceinline__ uint32_t &ss(int r) const { return SS[r * kWave + lane]; }
+    __device__ __forceinline__ uint2 tab(int i) const { return *reinterpret_cast<const uint2 *>(&T2[2 * i]); }
+};
+
+// The logic wave's board rows: loaded with the prologue's burst, staged into
+// L with the floor bits (the board allocation is padded to a multiple of 4
+// rows), and a rollout's store of the final board.
+template <int WT>
+struct BoardRows {
+    static constexpr int NBQ = ((WT ? WT : kMaxW) + 3) / 4;  // board 4-row groups
     uint4 bv[NBQ];
-    if constexpr (DO_L) {
+    __device__ __forceinline__ void load(const uint32_t *bsrc, const WaveCtx &c, int W) {
 #pragma unroll
         for (int q = 0; q < NBQ; ++q)
             if (WT || 4 * q < W)
-                bv[q] = *reinterpret_cast<const uint4 *>(bsrc + (size_t)(4 * q) * sd +
-                                                         (4 * q + 4 <= W ? loff : clamp_off(q, W)));
+                bv[q] = *reinterpret_cast<const uint4 *>(bsrc + (size_t)(4 * q) * c.sd +
+                                                         (4 * q + 4 <= W ? c.loff : c.clamp_off(q, W)));
     }
-    // (four named registers, not an array: an array indexed in two unrolled
-    // loops was once left in scratch memory)
-    static_assert(kHotQ == 4, "four staged counter groups");
-    uint4 sv0 = make_uint4(0u, 0u, 0u, 0u), sv1 = sv0, sv2 = sv0, sv3 = sv0;
-    auto ldq = [&](int q) -> uint4 {
-        return *reinterpret_cast<const uint4 *>(ssrc + (size_t)qbase(q) * sd +
-                                                (qbase(q) + 4 <= kHotRows ? loff : clamp_off(q, kHotRows)));
-    };
-    if (mine_q(0)) sv0 = ldq(0);
-    // (ablation 262144: st_step's draw wave does not load shape counts T J L Z -- timing only)
-    if (mine_q(1) && !(LCL && (kAblate & 262144u))) sv1 = ldq(1);
-    if (mine_q(2)) sv2 = ldq(2);
-    if (mine_q(3)) sv3 = ldq(3);
-    const int K = KSTEPS ? KSTEPS : p.k;
-    // two-wave st_step: the logic wave also builds the next-generation block
-    // (the draw wave's chain is the longer one).  (Measured and dropped: the
-    // draw wave running the action phase itself instead of waiting at B1 --
-    // the two concurrent action phases slowed the logic wave's by ~50%.)
-    constexpr bool STEP2 = KSTEPS == 1;
-    constexpr bool ACT = DO_L;
-    // unconditional (clamped) so it is issued with the others; masked at use
-    uint32_t act_next = 0;
-    if constexpr (ACT) act_next = p.actions[real ? e : p.n - 1];
-    // st_gate_actions (VEC instantiations, which every gated launch uses):
-    // the gate word, loaded with the prologue's burst (an empty range reads 0
-    // when the launch is not gated), tested after B0 -- before any global
-    // store of either wave
-    [[maybe_unused]] uint32_t gate_v = 0;
-    if constexpr (VEC) gate_v = __builtin_amdgcn_raw_buffer_load_b32(buf_rsrc(p.gate, 4u), 0u, 0, 0);
-    // two-wave st_step: the logic wave also fetches its piece word and clock
-    // per env (4 B/lane from lines the state loads fetch anyway), so the
-    // action phase starts from registers instead of an LDS read after B0
-    // (A/B: -0.2%)
-    constexpr bool DL = KSTEPS == 1 && ROLE == kRoleL;
-    [[maybe_unused]] uint32_t pw_d = 0, tm_d = 0;
-    if constexpr (DL) {
-        pw_d = p.piece[e];
-        tm_d = reinterpret_cast<const uint32_t *>(p.stats)[(int64_t)ST_STAT_TIME * sd + e];
-    }
-    // The piece table, lane i = entry i, from immediates (under the load
-    // latency; no memory access: a __constant__ load gets sunk by the
-    // compiler past the state loads' completion -- one more serialized round
-    // trip).  Two waves: the draw wave builds it (and the walls, and the f32
-    // nibble table).
-    constexpr bool BUILD = DO_D;
-    uint32_t tab_m = 0, tab_g = 0;
-    if constexpr (BUILD) {
-        // one v_writelane per entry (the constant in an SGPR: SALU): 56 VALU
-        // instead of a compare + two selects per entry (~140 VALU), on the
-        // draw wave's path to B0
-#pragma unroll
-        for (int i = 0; i < 28; ++i) {
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(tab_m) : "s"(kBox.m[i]), "i"(i));
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(tab_g) : "s"(kBox.g[i]), "i"(i));
-        }
-    }
-    const int lrow = lane >> 4, lcc = 4 * (lane & 15);  // this lane's row-in-group, env slot
-    if constexpr (DO_L) {
+    // rows >= W (allocation padding): with a dump slot they are sent there
+    // (st_step, k_rollout2) -- an address select, not a branch: a store
+    // under a branch gets its load sunk into the branch, one more round
+    // trip; without one (k_rollout) they are not staged.  The draw wave
+    // writes the wall columns in the same prologue.
+    template <bool DUMP>
+    __device__ __forceinline__ void stage(uint32_t *L, [[maybe_unused]] uint32_t *dump, const WaveCtx &c, int W,
+                                          uint32_t floorb) const {
 #pragma unroll
         for (int q = 0; q < NBQ; ++q) {
-            // rows >= W (allocation padding) land in the right-wall columns:
-            // one wave writes them first and the walls over them; the logic
-            // wave of two sends them to a dump slot (the draw wave writes the
-            // walls) -- an address select, not a branch: a store under a
-            // branch gets its load sunk into the branch, one more round trip
             if (WT || 4 * q < W) {
                 uint4 v = bv[q];
                 v.x |= floorb;
                 v.y |= floorb;
                 v.z |= floorb;
                 v.w |= floorb;
-                uint32_t *dst = &L[(4 * q + lrow + kPad) * kWave + lcc];
-                if constexpr (ROLE == kRoleL) dst = 4 * q + lrow < W ? dst : &sm.dump[lcc];
-                *reinterpret_cast<uint4 *>(dst) = v;
+                uint32_t *dst = &L[(4 * q + c.lrow + kPad) * kWave + c.lcc];
+                if constexpr (DUMP) {
+                    dst = 4 * q + c.lrow < W ? dst : &dump[c.lcc];
+                    *reinterpret_cast<uint4 *>(dst) = v;
+                } else {
+                    if (4 * q + c.lrow < W) *reinterpret_cast<uint4 *>(dst) = v;
+                }
             }
         }
     }
-    if constexpr (BUILD) {
+    // PADROWS: the allocation's padding rows (>= W) are written too
+    // (32-bit buffer offsets: 64-bit row offsets shared with the prologue
+    // would stay live (in SGPRs) across the step loop)
+    template <bool PADROWS>
+    static __device__ __forceinline__ void store(const KParams &p, const uint32_t *L, const WaveCtx &c, int W,
+                                                 uint32_t hmask) {
+        const auto rb = buf_rsrc(p.board, (uint32_t)((W + 3) & ~3) * (uint32_t)c.sd * 4u);
+        const uint32_t boff = (uint32_t)c.e0 * 4u + c.loff * 4u;
 #pragma unroll
-        for (int x = 0; x < kPad; ++x) {
-            L[x * kWave + lane] = ~0u;
-            L[(W + kPad + x) * kWave + lane] = ~0u;
-        }
-        if (lane < 28) {
-            sm.T2[2 * lane] = tab_m;
-            sm.T2[2 * lane + 1] = tab_g;
-        }
-        if constexpr (F32) {
-            if (lane < 16) {
-                sm.F4[4 * lane] = (float)(lane & 1);
-                sm.F4[4 * lane + 1] = (float)((lane >> 1) & 1);
-                sm.F4[4 * lane + 2] = (float)((lane >> 2) & 1);
-                sm.F4[4 * lane + 3] = (float)((lane >> 3) & 1);
+        for (int q = 0; q < NBQ; ++q) {
+            if ((WT || 4 * q < W) && (PADROWS || 4 * q + c.lrow < W)) {
+                uint4 v = *reinterpret_cast<const uint4 *>(&L[(4 * q + c.lrow + kPad) * kWave + c.lcc]);
+                v.x &= hmask;
+                v.y &= hmask;
+                v.z &= hmask;
+                v.w &= hmask;
+                buf_store16<kST>(rb, boff + (uint32_t)(4 * q) * (uint32_t)c.sd * 4u, v);
             }
         }
     }
-    auto stq = [&](int q, const uint4 &v) { *reinterpret_cast<uint4 *>(&SS[(qbase(q) + lrow) * kWave + lcc]) = v; };
-    if (mine_q(0)) stq(0, sv0);
-    if (mine_q(1)) stq(1, sv1);
-    if (mine_q(2)) stq(2, sv2);
-    if (mine_q(3)) stq(3, sv3);
-    if constexpr (OVP && DO_L) {
+};
+
+// The staged counter groups of a two-wave kernel (rows 4q .. 4q + 3): logic
+// 0-1, draw 2-3; with late rows (LCL, see step_logic) only what the draw wave
+// reads early: exactly the shape counts and the MT word (rows COUNT0 ..
+// MT_INDEX: two 4-row groups from row 6, a group's base row needs no
+// alignment) -- round 4 staged rows 4..15, 16 B per env more
+// (four named registers, not an array: an array indexed in two unrolled
+// loops was once left in scratch memory)
+template <bool LCL, bool DRAW>
+struct StagedRows {
+    static_assert(ST_STAT_MT_INDEX == ST_STAT_COUNT0 + 7, "counts and MT word: 8 consecutive rows");
+    static_assert(kHotQ == 4, "four staged counter groups");
+    uint4 sv0, sv1, sv2, sv3;
+    static constexpr bool mine(int q) { return LCL ? DRAW && (q == 1 || q == 2) : DRAW == (q >= 2); }
+    static constexpr int qbase(int q) { return LCL ? ST_STAT_COUNT0 + 4 * (q - 1) : 4 * q; }  // first stats row of staged group q
+    template <class C>
+    __device__ __forceinline__ void load(const C &c, const uint32_t *ssrc, [[maybe_unused]] uint32_t kAblate) {
+        sv0 = make_uint4(0u, 0u, 0u, 0u), sv1 = sv0, sv2 = sv0, sv3 = sv0;
+        auto ldq = [&](int q) -> uint4 {
+            return *reinterpret_cast<const uint4 *>(ssrc + (size_t)qbase(q) * c.sd +
+                                                    (qbase(q) + 4 <= kHotRows ? c.loff : c.clamp_off(q, kHotRows)));
+        };
+        if (mine(0)) sv0 = ldq(0);
+        // (ablation 262144: st_step's draw wave does not load shape counts T J L Z -- timing only)
+        if (mine(1) && !(LCL && (kAblate & 262144u))) sv1 = ldq(1);
+        if (mine(2)) sv2 = ldq(2);
+        if (mine(3)) sv3 = ldq(3);
+    }
+    template <class C>
+    __device__ __forceinline__ void store(const C &c) const {
+        auto stq = [&](int q, const uint4 &v) {
+            *reinterpret_cast<uint4 *>(&c.SS[(qbase(q) + c.lrow) * kWave + c.lcc]) = v;
+        };
+        if (mine(0)) stq(0, sv0);
+        if (mine(1)) stq(1, sv1);
+        if (mine(2)) stq(2, sv2);
+        if (mine(3)) stq(3, sv3);
+    }
+};
+
+// The draw wave's share of a prologue: the piece table, the wall columns and
+// the float32 nibble table.
+// The piece table, lane i = entry i, from immediates (under the load
+// latency; no memory access: a __constant__ load gets sunk by the
+// compiler past the state loads' completion -- one more serialized round
+// trip).
+template <int WT, bool F32, class LDS>
+__device__ __forceinline__ void build_tables(const KParams &p, LDS &sm, int lane) {
+    uint32_t *const L = sm.L;
+    const int W = WT ? WT : p.W;
+    uint32_t tab_m = 0, tab_g = 0;
+    // one v_writelane per entry (the constant in an SGPR: SALU): 56 VALU
+    // instead of a compare + two selects per entry (~140 VALU), on the
+    // draw wave's path to B0
+#pragma unroll
+    for (int i = 0; i < 28; ++i) {
+        asm("v_writelane_b32 %0, %1, %2" : "+v"(tab_m) : "s"(kBox.m[i]), "i"(i));
+        asm("v_writelane_b32 %0, %1, %2" : "+v"(tab_g) : "s"(kBox.g[i]), "i"(i));
+    }
+#pragma unroll
+    for (int x = 0; x < kPad; ++x) {
+        L[x * kWave + lane] = ~0u;
+        L[(W + kPad + x) * kWave + lane] = ~0u;
+    }
+    if (lane < 28) {
+        sm.T2[2 * lane] = tab_m;
+        sm.T2[2 * lane + 1] = tab_g;
+    }
+    if constexpr (F32) {
+        if (lane < 16) {
+            sm.F4[4 * lane] = (float)(lane & 1);
+            sm.F4[4 * lane + 1] = (float)((lane >> 1) & 1);
+            sm.F4[4 * lane + 2] = (float)((lane >> 2) & 1);
+            sm.F4[4 * lane + 3] = (float)((lane >> 3) & 1);
+        }
+    }
+}
+
+// A rollout's epilogue: the staged counter rows, each wave the rows it owns
+// (logic: 0-5 and the piece row, draw: the shape counts and the MT word).
+// (row 15, ep_time, is never staged: it is stored per lane on a reset)
+template <bool DRAW, class C>
+__device__ __forceinline__ void store_staged_rows(const KParams &p, const C &c) {
+    constexpr uint32_t kRowsD = ((1u << 7) - 1u) << ST_STAT_COUNT0 | 1u << ST_STAT_MT_INDEX;
+    constexpr uint32_t kOwn = DRAW ? kRowsD : ((1u << kHotRows) - 1u) & ~kRowsD;
+    const auto rs = buf_rsrc(p.stats, (uint32_t)kHotRows * (uint32_t)c.sd * 4u);
+    const uint32_t soff = (uint32_t)c.e0 * 4u + c.loff * 4u;
+#pragma unroll
+    for (int q = 0; q < kHotQ; ++q) {
+        if (((kOwn >> (4 * q)) & 0xFu) == 0u) continue;
+        const bool st = (kOwn >> (4 * q + c.lrow)) & 1u;
+        buf_store16<kST>(rs, st ? soff + (uint32_t)(4 * q) * (uint32_t)c.sd * 4u : kOff,
+                         *reinterpret_cast<const uint4 *>(&c.SS[(4 * q + c.lrow) * kWave + c.lcc]));
+    }
+}
+
+// st_gate_actions (VEC instantiations, which every gated launch uses):
+// the gate word, loaded with the prologue's burst (an empty range reads 0
+// when the launch is not gated), tested after B0 -- before any global
+// store of either wave
+template <bool VEC>
+__device__ __forceinline__ uint32_t gate_load([[maybe_unused]] const KParams &p) {
+    if constexpr (VEC) return __builtin_amdgcn_raw_buffer_load_b32(buf_rsrc(p.gate, 4u), 0u, 0, 0);
+    return 0u;
+}
+// a gate that saw an action outside 0..6: no env steps (both waves
+// leave after B0, before B1 and before any global store)
+template <bool VEC>
+__device__ __forceinline__ bool gate_shut([[maybe_unused]] const KParams &p, [[maybe_unused]] uint32_t gate_v) {
+    if constexpr (VEC) return p.gate && __builtin_amdgcn_readfirstlane(gate_v) == p.gate_epoch;
+    return false;
+}
+
+// The stamp build's dump of a step wave (k_step, k_rollout2).
+template <bool STAMP, int KSTEPS, bool DRAW>
+__device__ __forceinline__ void dump_stamps(const KParams &p, int lane, int K, uint64_t (&tstamp)[12],
+                                            uint32_t (&tacc)[12], uint64_t &tlast, uint64_t rt0,
+                                            uint64_t draw_kind) {
+    if constexpr (STAMP && KSTEPS != 1) {
+        // rollout stamp build: words [0, 16) of the workgroup's slot the
+        // logic wave's per-phase cycle totals (stamp index i), [16, 32) the
+        // draw wave's; word 12 / 28: s_memrealtime span, 13 / 29: steps
+        ST_STAMP(6);
+        uint64_t *slot = p.stamps + (int64_t)blockIdx.x * kStampWords + (DRAW ? 16 : 0);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 12; ++i) slot[i] = tacc[i];
+            slot[12] = __builtin_amdgcn_s_memrealtime() - rt0;
+            slot[13] = (uint64_t)K;
+        }
+    }
+    if constexpr (STAMP && KSTEPS == 1) {
+        // words [0, 16) of the workgroup's slot: the logic wave (stamps
+        // 0-9, realtime start/end, HW_ID, XCC_ID, draw kind); [16, 32): the
+        // draw wave (stamps 0-11, realtime start/end)
+        ST_STAMP(6);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ST_STAMP(7);
+        uint64_t *slot = p.stamps + (int64_t)blockIdx.x * kStampWords + (DRAW ? 16 : 0);
+        if (lane == 0) {
+            if constexpr (DRAW) {
+#pragma unroll
+                for (int i = 0; i < 12; ++i) slot[i] = tstamp[i];
+                slot[12] = rt0;
+                slot[13] = __builtin_amdgcn_s_memrealtime();
+                slot[14] = draw_kind;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 10; ++i) slot[i] = tstamp[i];
+                slot[10] = rt0;
+                slot[11] = __builtin_amdgcn_s_memrealtime();
+                slot[12] = __builtin_amdgcn_s_getreg(0xF804);  // HW_ID
+                slot[13] = __builtin_amdgcn_s_getreg(0xF814);  // XCC_ID
+                slot[14] = tstamp[10];  // round 6: reward / done issued
+                slot[15] = tstamp[11];  // round 6: the store phase's LDS reads arrived
+            }
+        }
+    }
+}
+
+// ---- the two waves of k_step and k_rollout2: step_logic and step_draw ----
+// KSTEPS == 1: TetrisEngine.step once (st_step); KSTEPS == 0: p.k consecutive
+// steps (k_rollout2, st_rollout above 4 workgroups per CU) with the board and
+// counters kept in LDS between steps, actions read one step ahead, and
+// per-step outputs at [t].  State is
+// loaded once at the start and stored once at the end.
+// SC0: see step_flags.
+// VEC (st_step_vec): the vector env's outputs -- with
+// p.final_obs, an env reset in this step returns the reset obs (the empty
+// board clear() returns, tetris_env.py:306-315, :405-411) and its terminal
+// obs goes to final_obs; with p.info, every counter row after the step is
+// written to info [ST_NSTAT][n] (the ep_* rows: the finished episode's where
+// the env was reset, else 0).
+//
+// The contract between the two (one workgroup = the logic wave, threads
+// 0..63, and the draw wave, threads 64..127, of the same 64 envs):
+//  - B0 (wg_barrier) once, after each wave has staged its share of the state
+//    -- logic: the board, its counter groups, the zeroed overlay plane; draw:
+//    its counter groups, the walls, the piece table, the F4 table;
+//  - VEC: after B0 both take the gate's early return, before B1 and before any
+//    global store of either wave;
+//  - B1 (wg_barrier) once per step in both: before it the logic wave
+//    publishes the lock ballot in lockm[t & 1] (owner: logic; the draw wave
+//    reads it after B1);
+//  - logic -> draw: drawm (the lanes whose lock consumed the preview) under
+//    the flag f1 = t + 1, written and waited for only without same-step
+//    auto-reset (with it every locking lane draws);
+//  - draw -> logic: pick1 (the first draw of a lane without a valid preview)
+//    under the flag f2 = t + 1, set every step, waited for only where a lane
+//    needs it (rare);
+//  - rollouts: mtw[t & 1] (owner: draw) is the MT word after step t, which
+//    the logic wave's step t + 1 reads after its B1;
+//  - each wave zeroes the flag it owns (logic f1, draw f2) before B0.
+// LATE COUNTERS (LCL), st_step (not st_step_vec, whose info snapshot needs
+// every counter of every env).  The prologue's load burst carries only what
+// every env needs at the step start -- board, action, time, piece word,
+// MT word -- and the lock-only counter rows are read per locking lane
+// once the lock decision is known (logic: score .. deaths, issued before
+// B1, needed at the end of the lock path; draw: the shape counts, issued
+// with the MT window after B1)
+// (round 4, profiles/r04/ab_late_counters.txt: K = 2,000 4.642-4.643 ->
+// 4.605-4.635 us; reading the draw wave's shape counts late as well was
+// +6% -- its post-B1 chain, window + counts + draw parameters, became the
+// step's -- and was dropped)
+
+// The logic wave: action, lock path, board / obs / counter outputs.
+template <int WT, int HT, bool F32, bool STAMP, int KSTEPS, bool SC0, bool VEC = false>
+__device__ __forceinline__ void step_logic(const KParams &p, StepLds<WT, F32, KSTEPS> &sm) {
+    static_assert(!VEC || KSTEPS == 1, "VEC: st_step only");
+    [[maybe_unused]] uint64_t tstamp[12] = {};
+    [[maybe_unused]] uint32_t tacc[12] = {};  // rollout stamp build: per-phase cycle totals
+    [[maybe_unused]] uint64_t tlast = 0;
+    constexpr bool S32 = HT != 0 && HT <= 25;  // see pc_bits
+    const uint32_t kFlags = step_flags<SC0>(p);
+    const uint32_t kAblate = ablate_bits(p);
+    [[maybe_unused]] uint64_t rt0 = 0;
+    if constexpr (STAMP) {
+        rt0 = __builtin_amdgcn_s_memrealtime();
+        tlast = __builtin_amdgcn_s_memtime();
+    }
+    ST_STAMP(0);
+    if constexpr (KSTEPS == 1) __builtin_amdgcn_s_setprio(kLogicPrio);
+    uint32_t *const L = sm.L;
+    const int W = WT ? WT : p.W, H = HT ? HT : p.H;
+    const uint32_t hmask = (1u << H) - 1u, floorb = ~hmask;
+    const WaveCtx wc(p, sm);
+    const int lane = wc.lane, lrow = wc.lrow, lcc = wc.lcc;
+    const int64_t e0 = wc.e0, e = wc.e, sd = wc.sd;
+    const bool real = wc.real;
+    const uint32_t loff = wc.loff;
+
+    // ---- loads: the board and counter groups 0-1 (time .. count1); the draw
+    // wave loads groups 2-3 (count2 .. MT word, piece).  Counter rows: 0..14
+    // plus row 15 (unused). ----
+    constexpr int NBQ = BoardRows<WT>::NBQ;
+    // (ablation 1024: every wave's counter groups from the first workgroup's
+    // lines -- the counter rows' HBM reads gone, timing only)
+    const uint32_t *ssrc = reinterpret_cast<const uint32_t *>(p.stats) + ((kAblate & 1024u) ? 0 : e0);
+    constexpr bool OVP = KSTEPS == 1;
+    constexpr bool LCL = KSTEPS == 1 && !VEC;  // late counters, see above
+    BoardRows<WT> br;
+    br.load(p.board + e0, wc, W);
+    StagedRows<LCL, false> sq;
+    sq.load(wc, ssrc, kAblate);
+    const int K = KSTEPS ? KSTEPS : p.k;
+    // (Measured and dropped: the
+    // draw wave running the action phase itself instead of waiting at B1 --
+    // the two concurrent action phases slowed the logic wave's by ~50%.)
+    // unconditional (clamped) so it is issued with the others; masked at use
+    uint32_t act_next = p.actions[real ? e : p.n - 1];
+    const uint32_t gate_v = gate_load<VEC>(p);
+    // st_step: the logic wave also fetches its piece word and clock
+    // per env (4 B/lane from lines the state loads fetch anyway), so the
+    // action phase starts from registers instead of an LDS read after B0
+    // (A/B: -0.2%)
+    [[maybe_unused]] uint32_t pw_d = 0, tm_d = 0;
+    if constexpr (KSTEPS == 1) {
+        pw_d = p.piece[e];
+        tm_d = reinterpret_cast<const uint32_t *>(p.stats)[(int64_t)ST_STAT_TIME * sd + e];
+    }
+    br.template stage<true>(L, sm.dump, wc, W, floorb);
+    sq.store(wc);
+    if constexpr (OVP) {
 #pragma unroll
         for (int q = 0; q < NBQ; ++q)
             if ((WT || 4 * q < W) && 4 * q + lrow < W)
                 *reinterpret_cast<uint4 *>(&sm.OV[(4 * q + lrow + kPad) * kWave + lcc]) = make_uint4(0u, 0u, 0u, 0u);
     }
-    if (ROLE == kRoleL && lane == 0) sm.f1 = 0u;
-    if (ROLE == kRoleD && lane == 0) sm.f2 = 0u;
+    if (lane == 0) sm.f1 = 0u;
     wg_barrier();  // B0: the staged state is complete
-    if constexpr (VEC) {
-        // a gate that saw an action outside 0..6: no env steps (both waves
-        // leave here, before B1 and before any global store)
-        if (p.gate && __builtin_amdgcn_readfirstlane(gate_v) == p.gate_epoch) return;
-    }
-    auto ss = [&](int r) -> uint32_t & { return SS[r * kWave + lane]; };
-    auto tab = [&](int i) -> uint2 { return *reinterpret_cast<const uint2 *>(&sm.T2[2 * i]); };
+    if (gate_shut<VEC>(p, gate_v)) return;
     // an action outside value_action_map in any step of this launch (the
     // reference's KeyError, tetris_env.py:245; the step treats it as idle)
-    [[maybe_unused]] bool bad_act = false;
+    bool bad_act = false;
     for (int t = 0; t < K; ++t) {
-    // ---------------- logic: action, gravity, lock decision ----------------
-    uint32_t act = 6u;
-    if constexpr (ACT) {
-        act = real ? act_next : 6u;
-        bad_act |= act > 6u;
-        if (KSTEPS != 1 && t + 1 < K) act_next = p.actions[(int64_t)(t + 1) * p.n + (real ? e : p.n - 1)];
-    }
+    // ---------------- action, gravity, lock decision ----------------
+    uint32_t act = real ? act_next : 6u;
+    bad_act |= act > 6u;
+    if (KSTEPS != 1 && t + 1 < K) act_next = p.actions[(int64_t)(t + 1) * p.n + (real ? e : p.n - 1)];
     uint32_t *const obs_t = p.obs ? p.obs + (int64_t)t * W * p.n : nullptr;
-    const uint32_t pw = DL ? pw_d : ss(kPieceRow);
-    int32_t time = (int32_t)(DL ? tm_d : ss(ST_STAT_TIME));
+    const uint32_t pw = KSTEPS == 1 ? pw_d : wc.ss(kPieceRow);
+    int32_t time = (int32_t)(KSTEPS == 1 ? tm_d : wc.ss(ST_STAT_TIME));
     const int id = (int)(pw & 7u);
     int rot = (int)((pw >> 3) & 3u);
     int ax = (int)((pw >> 5) & 63u);
@@ -1262,7 +1573,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
     // MT word at the start of the step (the logic wave uses only the preview
     // bits; in a two-wave step the draw wave replaces the row after B1, and in
     // a two-wave rollout it hands step t-1's word over in mtw: read after B1)
-    uint32_t mt0 = ss(ST_STAT_MT_INDEX);
+    uint32_t mt0 = wc.ss(ST_STAT_MT_INDEX);
     if constexpr (STAMP && KSTEPS == 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     ST_STAMP(1);
 
@@ -1272,55 +1583,25 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
     // st_step's obs overlay of a spawn: its preview's descriptor, read in the
     // action phase's LDS round trip (not on the store phase's chain)
     [[maybe_unused]] uint2 pd_pv = make_uint2(0u, 0u);
-    if constexpr (ACT) {
-        // ---- action (tetris_env.py:245; value_action_map :152-160) + drop ----
+    {
+        // ---- action + drop, gravity + lock delay (move_cand, move_resolve) ----
         // Current and candidate descriptors and their columns are read in one
-        // LDS round trip each; the collision and drop tests are then pure VALU.
-        const bool tries = act == 0u || act == 1u || act == 4u || act == 5u;
-        const int cx = ax + (act == 0u ? -1 : (act == 1u ? 1 : 0));
-        const int cr = (rot + (act == 4u ? 1 : 0) + (act == 5u ? 3 : 0)) & 3;  // (selects: the ternary chain became an exec-mask branch)
-        desc = tab(id * 4 + rot);
-        const uint2 cdesc = tab(id * 4 + cr);
-        if constexpr (OVP && DO_L) pd_pv = tab(pv_id(mt0) * 4);
+        // LDS round trip each.
+        const MoveCand mc = move_cand(act, ax, rot);
+        desc = wc.tab(id * 4 + rot);
+        const uint2 cdesc = wc.tab(id * 4 + mc.cr);
+        if constexpr (OVP) pd_pv = wc.tab(pv_id(mt0) * 4);
         uint32_t cur[4], cand[4];
         read_box(L, lane, desc.y, ax, cur);
-        read_box(L, lane, cdesc.y, cx, cand);
-        // branch-free: select the accepted position's descriptor and columns, then
-        // one drop test (both arms would otherwise run in a divergent wave)
-        const bool ok = tries && !collides_v<S32>(cdesc.x, ay, cand);
-        ax = ok ? cx : ax;
-        rot = ok ? cr : rot;
-        desc.x = ok ? cdesc.x : desc.x;
-        desc.y = ok ? cdesc.y : desc.y;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) cur[j] = ok ? cand[j] : cur[j];
-        int d = drop_box(desc.y, ay, cur);
-        if (act == 2u) {                 // hard_drop :54-59
-            ay += d;
-            d = 0;
-        } else if (act == 3u && d > 0) { // soft_drop :49-51
-            ay += 1;
-            d -= 1;
-        }
-        // ---- gravity + lock delay (tetris_env.py:247-262) ----
-        if (d > 0) {
-            ay += 1;
-            d -= 1;
-            if (kFlags & ST_STEP_RESET) lock = 0;
-        }
-        time += 1;
-        rew = (kFlags & ST_REWARD_STEP) ? 1 : 0;
-        if (d == 0) {
-            const int l1 = lock + 1;  // (x + 1) % lock_mod; x < lock_mod unless set_state said otherwise
-            lock = lock_next(l1, p.lock_mod);
-            locknow = lock == 0 && !(kAblate & 1u);
-        }
+        read_box(L, lane, cdesc.y, mc.cx, cand);
+        locknow = move_resolve<S32>(act, mc, cdesc, cand, desc, cur, rot, ax, ay, lock, time, rew, kFlags, kAblate,
+                                    p.lock_mod);
     }
     ST_STAMP(2);
     // LC: the logic wave's lock-path counters, per locking lane (an
     // out-of-range offset elsewhere: no traffic, 0)
     [[maybe_unused]] uint32_t lcv[5] = {};
-    if constexpr (LCL && DO_L) {
+    if constexpr (LCL) {
         const auto rs = buf_rsrc(p.stats, (uint32_t)kHotRows * (uint32_t)sd * 4u);
         // (ablation 8192: from the first workgroup's lines -- their HBM reads gone, timing only)
         const uint32_t eo = (kAblate & 8192u) ? (uint32_t)lane * 4u : (uint32_t)e * 4u;
@@ -1331,29 +1612,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
         for (int j = 0; j < 5; ++j)
             lcv[j] = __builtin_amdgcn_raw_buffer_load_b32(rs, lo, (uint32_t)(ST_STAT_SCORE + j) * (uint32_t)sd * 4u, 0);
     }
-    // the draw wave's next-generation chunk of this step: operands issued
-    // before B1, so they arrive while it waits for the lock decision
-    [[maybe_unused]] MtChunk chunk;
-    [[maybe_unused]] MtRes mrs;
-    // ... and the count-dependent part of the preview draw (in st_step while
-    // the draw wave waits for the lock decision): a lane that draws spawns its
-    // preview first, so its draw sees the counts now + that shape (lanes
-    // without a valid preview redo this after their first draw, below)
-    [[maybe_unused]] int32_t cnt[7];
-    [[maybe_unused]] DrawPar dpar;
-    [[maybe_unused]] int32_t csid = 0;  // the spawned shape's count after the spawn
-    if constexpr (DO_D) {
-        mrs = mt_res(p.mt + e0 * kMtPitch, lane);
-        mt_chunk_issue(mrs, mt0, real && !(kAblate & (2u | 1048576u)), lane, chunk);  // (1048576: no chunks, timing only)
-        const int s0 = pv_id(mt0);
-#pragma unroll
-        for (int i = 0; i < 7; ++i) cnt[i] = (int32_t)ss(ST_STAT_COUNT0 + i) + (i == s0);  // _new_piece :199
-        csid = cnt[0];
-#pragma unroll
-        for (int i = 1; i < 7; ++i) csid = s0 == i ? cnt[i] : csid;
-        dpar = draw_par(cnt);
-    }
-    if constexpr (DO_L) {
+    {
         const uint64_t m = __ballot(locknow);
         if (lane == 0) {
             sm.lockm[t & 1][0] = (uint32_t)m;
@@ -1361,130 +1620,50 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
         }
     }
     wg_barrier();  // B1: the draw wave learns which lanes lock
-    if constexpr (DO_D || KSTEPS != 1) ST_STAMP(10);
-    if constexpr (DO_D) __builtin_amdgcn_s_setprio(kDrawPrio);
-    if constexpr (DO_D) {
-        const uint32_t w = lane < 32 ? sm.lockm[t & 1][0] : sm.lockm[t & 1][1];
-        locknow = (w >> (lane & 31)) & 1u;
-    }
-    if constexpr (DO_L && KSTEPS != 1) {
+    if constexpr (KSTEPS != 1) ST_STAMP(10);
+    if constexpr (KSTEPS != 1) {
         if (t > 0) mt0 = sm.mtw[(t - 1) & 1][lane];
     }
-
-    // ---------------- draw: MT window, issued now ----------------
-    // Every locking lane draws (its next preview, or -- without a valid
-    // preview -- its piece first); the window is consumed after the lock path
-    // in one wave, or right away by the draw wave.
-    uint32_t mtst = mt0;  // packed (mt_pack + preview bits)
-    const bool want_pre = locknow && !(kAblate & 2u);
-    constexpr int kWin = STEP2 ? 8 : 16;
-    MtPre pre;
-    // (ablation 524288: the window's words read as zeros, no traffic -- timing only)
-    if constexpr (DO_D) mt_pre_load<kWin>(mrs, mtst, want_pre && !(kAblate & 524288u), pre);
 
     // st_step's wide packed obs path (16-B stores of 4-env groups, below)
     [[maybe_unused]] const bool wide_obs1 = OVP && (p.n & 3) == 0 && e0 + kWave <= p.n &&
                                             (reinterpret_cast<uintptr_t>(p.obs) & 15u) == 0 &&
                                             (!VEC || (reinterpret_cast<uintptr_t>(p.final_obs) & 15u) == 0);
 
-    // ---------------- logic: lock path (tetris_env.py:263-299) ----------------
+    // ---------------- lock path (tetris_env.py:263-299) ----------------
     bool died = false, spawn = false;
     int32_t score = 0, lines = 0, holes = 0, height = 0, deaths = 0;
     int32_t o_score = 0, o_lines = 0, o_holes = 0, o_height = 0, o_deaths = 0;  // (dirty tests)
     [[maybe_unused]] bool hset = false;  // LC: height set by the lock path
     uint32_t bdirty = 0;  // st_step: board columns this step changes (stores skip the rest)
-    if (DO_L && locknow) {
+    if (locknow) {
         // (LC: score / lines / deaths count from 0 here -- deltas, added to
         // the late-loaded values where they are stored, long after the lock
         // path; the old holes / height are read only by the scoring flags
         // that need them)
         if constexpr (!LCL) {
-            score = o_score = (int32_t)ss(ST_STAT_SCORE);
-            lines = o_lines = (int32_t)ss(ST_STAT_LINES);
-            holes = o_holes = (int32_t)ss(ST_STAT_HOLES);
-            height = o_height = (int32_t)ss(ST_STAT_PIECE_HEIGHT);
-            deaths = o_deaths = (int32_t)ss(ST_STAT_DEATHS);
+            score = o_score = (int32_t)wc.ss(ST_STAT_SCORE);
+            lines = o_lines = (int32_t)wc.ss(ST_STAT_LINES);
+            holes = o_holes = (int32_t)wc.ss(ST_STAT_HOLES);
+            height = o_height = (int32_t)wc.ss(ST_STAT_PIECE_HEIGHT);
+            deaths = o_deaths = (int32_t)wc.ss(ST_STAT_DEATHS);
         }
-        paint_box<S32>(L, lane, desc.x, desc.y, ax, ay, hmask);
-        // Column words carry the floor bits, so the topmost cell of column v
-        // is ctz(v) (H when empty) and its holes are H - ctz(v) - popc(v & hmask):
-        // summed, holes = W*H - sum ctz(v) - (sum popc(v) - W*(32-H)).
-        uint32_t andv = ~0u, orv = 0, sctz = 0, spop = 0;
-        // (compile-time width: all W column reads issued before any is used,
-        // one LDS round trip -- left to itself the scheduler reused the first
-        // reads' registers as accumulators and issued the last pair after
-        // waiting for the others; the clear path reuses the words)
-        [[maybe_unused]] uint32_t cw[WT ? WT : 1];
-        if constexpr (WT != 0) {
-#pragma unroll
-            for (int x = 0; x < WT; ++x) cw[x] = lcol(L, x, lane);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int x = 0; x < WT; ++x) {
-                const uint32_t v = cw[x];
-                andv &= v;
-                orv |= v;
-                sctz += __builtin_ctz(v);
-                spop += __builtin_popcount(v);
-            }
-        } else {
-#pragma unroll 8
-            for (int x = 0; x < W; ++x) {
-                const uint32_t v = lcol(L, x, lane);
-                andv &= v;
-                orv |= v;
-                sctz += __builtin_ctz(v);
-                spop += __builtin_popcount(v);
-            }
-        }
-        andv &= hmask;
+        LockCols<WT> lb;
+        lock_board<WT, S32, true>(L, lane, W, hmask, floorb, desc, ax, ay, lb);
         if constexpr (KSTEPS == 1) {
             // the columns holding the locked piece's cells: its box's first n
             // (byte c of m is column c's cells, the empty ones last)
             bdirty = (0xFu >> (__builtin_clz(desc.x) >> 3)) << box_x0(desc.y, ax);
-            if (andv) bdirty = ~0u;
+            if (lb.ncl) bdirty = ~0u;
         }
-        int32_t ncl = 0;
-        if (andv) {  // full rows: compact, recount
-            ncl = __builtin_popcount(andv);
-            orv = 0;
-            sctz = spop = 0;
-            if constexpr (WT != 0) {
-                // the columns in registers, one full row per round for all of
-                // them (compact()'s steps in the same order): the rounds are
-                // the wave's largest clear count, not one loop per column
-                uint32_t c[WT];
-#pragma unroll
-                for (int x = 0; x < WT; ++x) c[x] = cw[x] & hmask;
-                uint32_t full = andv;
-                while (full) {
-                    const int r = __builtin_ctz(full);
-                    full &= full - 1u;
-                    const uint32_t above = (1u << r) - 1u;
-                    const uint32_t keep = ~(above | (1u << r));
-#pragma unroll
-                    for (int x = 0; x < WT; ++x) c[x] = (c[x] & keep) | ((c[x] & above) << 1);
-                }
-#pragma unroll
-                for (int x = 0; x < WT; ++x) {
-                    const uint32_t v = c[x] | floorb;
-                    lcol(L, x, lane) = v;
-                    orv |= v;
-                    sctz += __builtin_ctz(v);
-                    spop += __builtin_popcount(v);
-                }
-            } else {
-#pragma unroll 8
-                for (int x = 0; x < W; ++x) {
-                    const uint32_t v = compact(lcol(L, x, lane) & hmask, andv) | floorb;
-                    lcol(L, x, lane) = v;
-                    orv |= v;
-                    sctz += __builtin_ctz(v);
-                    spop += __builtin_popcount(v);
-                }
-            }
-            lines += ncl;
-        }
+        // The scoring part, inline: the same rules as lock_score (keep the two
+        // in step).  Through lock_score, st_step's C4 kernel measured 0.6%
+        // slower and, with the helper reshaped, its float32 kernel 0.9%
+        // (profiles/r08/ab_refactor.txt); k_rollout uses lock_score.
+        const int32_t ncl = lb.ncl;
+        uint32_t orv = lb.orv;
+        const uint32_t sctz = lb.sctz, spop = lb.spop;
+        lines += ncl;
         orv &= hmask;
         const int32_t nh = W * H - (int32_t)sctz - ((int32_t)spop - W * (32 - H));
         if (kFlags & ST_ADVANCED_CLEARS) {  // :266-269, 2.5 * [0,40,100,300,1200]
@@ -1528,8 +1707,8 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
     const bool reset_now = died && p.autoreset == ST_AUTORESET_SAME_STEP;
     // a lock consumes the preview (spawn, or the same-step reset's new piece);
     // a death without auto-reset does not (the next st_reset takes it)
-    bool draw = spawn || reset_now;
-    if (DO_L && p.autoreset != ST_AUTORESET_SAME_STEP) {
+    const bool draw = spawn || reset_now;
+    if (p.autoreset != ST_AUTORESET_SAME_STEP) {
         const uint64_t m = __ballot(draw);
         if (lane == 0) {
             sm.drawm[0] = (uint32_t)m;
@@ -1539,7 +1718,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
     }
     uint2 odesc = desc;
     int oax = ax, oay = ay;
-    if constexpr (DO_L) {
+    {
         // reward / done never depend on the piece drawn below.  Buffer stores
         // (buf_rsrc): vmcnt counts loads and stores in issue order, and a store
         // skipped on some path would make a later load's wait vmcnt(0).
@@ -1549,7 +1728,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
         __builtin_amdgcn_raw_buffer_store_b8((char)(died ? 1 : 0), rd, real ? (uint32_t)e : kOff, 0, kRD);
         if constexpr (KSTEPS == 1) ST_STAMP(10);  // (logic wave, round 6: reward / done stores issued)
     }
-    if constexpr (DO_L && KSTEPS == 1) {
+    if constexpr (KSTEPS == 1) {
         // The post-step board never depends on the spawned piece either (a
         // spawn only overlays row 0, which is empty after a non-fatal lock,
         // :277), so st_step stores it here: non-locking lanes and spawns: L; a
@@ -1571,7 +1750,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
             const bool need1 = draw && !pv_ok(mt0);
             if (__ballot(need1)) {
                 lds_flag_wait(&sm.f2, (uint32_t)t + 1u);
-                if (need1) pd = tab((int)sm.pick1[lane] * 4);
+                if (need1) pd = wc.tab((int)sm.pick1[lane] * 4);
             }
             const uint32_t om = spawn ? pd.x : desc.x, og = spawn ? pd.y : desc.y;
             const int ox = spawn ? W / 2 : ax, oy = spawn ? 0 : ay;
@@ -1669,107 +1848,11 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
     }
 
     ST_STAMP(8);  // (stamp 8: between the early stores and the draw)
-    // ---------------- draw (tetris_env.py:183-199, :299 _new_piece, :306-315 clear) ----------------
-    // spawn id: the preview; lanes without one draw their piece first
+    // ---------------- spawn (tetris_env.py:299 _new_piece, :306-315 clear) ----------------
+    // spawn id: the preview; lanes without one take the draw wave's first
+    // draw (rare)
     int sid = pv_id(mt0);
-    if constexpr (DO_D) {
-        // speculative in the draw wave (it does not know yet which locking
-        // lanes die without auto-reset): committed below only where `draw`
-        const bool dr_spec = locknow;
-        if constexpr (STAMP) {  // diagnostic split of the draw: MT-word wait | compute
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            ST_STAMP(9);
-        }
-        [[maybe_unused]] const uint32_t mt_before = mtst;
-        uint32_t mt_new = mtst;
-        if (!(kAblate & 2u)) {
-            mt_win_consume<kWin>(pre);
-            const bool need1 = dr_spec && !pv_ok(mt0);
-            if (__ballot(need1)) {  // rare: after st_seed / st_mt_sync / a host-written state
-                // the piece first, with the counts before the spawn
-                int32_t c0[7];
-#pragma unroll
-                for (int i = 0; i < 7; ++i) c0[i] = (int32_t)ss(ST_STAT_COUNT0 + i);
-                const int pk = draw_shape<kWin, false>(need1, c0, mtst, p.mt + e0 * kMtPitch, sm.S, lane, pre, false);
-                if (need1) {
-                    sid = pk;
-#pragma unroll
-                    for (int i = 0; i < 7; ++i) cnt[i] = c0[i] + (i == pk);  // _new_piece :199
-#pragma unroll
-                    for (int i = 0; i < 7; ++i) csid = pk == i ? cnt[i] : csid;
-                }
-                dpar = draw_par(cnt);
-            }
-            sm.pick1[lane] = (uint32_t)sid;
-            if (lane == 0) lds_flag_set(&sm.f2, (uint32_t)t + 1u);
-            const uint32_t m0 = mtst;
-            const int npv = draw_core<kWin>(dr_spec, dpar, mtst, p.mt + e0 * kMtPitch, sm.S, lane, pre,
-                                            want_pre && pv_ok(mt0));
-            mt_new = pv_pack(mtst, npv, mt_consumed(m0, mtst));
-        } else {
-            sm.pick1[lane] = (uint32_t)sid;
-            if (lane == 0) lds_flag_set(&sm.f2, (uint32_t)t + 1u);
-        }
-        // this step's next-generation chunk (its operands arrived long ago);
-        // its env's progress advances unless that env's own draw switched
-        // generations (finishing the successor itself: same words)
-        const int chunk_pg = mt_chunk_store<KSTEPS == 1 ? kST : 0>(mrs, lane, chunk);
-        const bool chunk_me = lane == chunk.l;
-        ST_STAMP(4);
-        if constexpr (STAMP) {  // 1: a draw started a generation, 2: a draw ran past its 8 words
-            const int i0 = (int)(mt_before & 0x3FFu), i1 = (int)(mt_new & 0x3FFu);
-            draw_kind = (__ballot(dr_spec && i1 < i0) ? 1u : 0u) | (__ballot(dr_spec && i1 >= i0 && i1 - i0 > 8) ? 2u : 0u);
-        }
-        // commit: lanes whose lock consumed the preview
-        bool dr = draw;
-        dr = locknow;
-        if (p.autoreset != ST_AUTORESET_SAME_STEP) {
-            lds_flag_wait(&sm.f1, (uint32_t)t + 1u);
-            const uint32_t w = lane < 32 ? sm.drawm[0] : sm.drawm[1];
-            dr = (w >> (lane & 31)) & 1u;
-        }
-        // (a lane that locks but does not draw -- a death without auto-reset
-        // -- keeps its old MT word: its speculative draw is dropped)
-        uint32_t mt_out = dr ? mt_new : mt0;
-        if (chunk_me && (mt_out & (1u << 20)) == (mt0 & (1u << 20))) {
-            int i2, pg2, c2;
-            mt_unpack(mt_out, i2, pg2, c2);
-            mt_out = mt_keep(mt_out, mt_pack(i2, chunk_pg, c2));
-        }
-        if constexpr (STEP2) {
-            // st_step: this wave's changed counter rows straight from the
-            // registers, one coalesced dword per lane and row (no staging
-            // through LDS at the end of the chain): the MT word, and the
-            // count of the spawned shape (csid, counted above)
-            const auto rs = buf_rsrc(p.stats, (uint32_t)kHotRows * (uint32_t)sd * 4u);
-            const uint32_t eo = (uint32_t)e * 4u;
-            // (ablation 2048: the lock-path counter stores dropped, timing only)
-            const bool cst = !(kAblate & (2048u | 32768u));
-            const bool mst = cst && !(kAblate & 131072u) && (dr || chunk_me);
-            const bool kst = cst && !(kAblate & 65536u) && dr;
-            __builtin_amdgcn_raw_buffer_store_b32(mt_out, rs, mst ? eo + (uint32_t)ST_STAT_MT_INDEX * (uint32_t)sd * 4u : kOff,
-                                                  0, kST);
-            __builtin_amdgcn_raw_buffer_store_b32(
-                (uint32_t)csid, rs, kst ? eo + (uint32_t)(ST_STAT_COUNT0 + sid) * (uint32_t)sd * 4u : kOff, 0, kST);
-            if constexpr (VEC) {  // st_step_vec's info snapshot: the shape counts after the step
-                const auto ri = buf_rsrc(p.info, (uint32_t)ST_NSTAT * (uint32_t)p.n * 4u);
-#pragma unroll
-                for (int i = 0; i < 7; ++i)
-                    __builtin_amdgcn_raw_buffer_store_b32(
-                        (uint32_t)(dr ? cnt[i] : (int32_t)ss(ST_STAT_COUNT0 + i)), ri,
-                        real ? ((uint32_t)(ST_STAT_COUNT0 + i) * (uint32_t)p.n + (uint32_t)e) * 4u : kOff, 0, kNT);
-            }
-        } else {
-            // rollout: the staged rows (stored at the end of the launch)
-            if (dr || chunk_me) ss(ST_STAT_MT_INDEX) = mt_out;
-            if (dr) atomicAdd(&ss(ST_STAT_COUNT0 + sid), 1u);  // shape_counts[name] += 1, :199 (ds_add, no return)
-            sm.mtw[t & 1][lane] = mt_out;  // the logic wave's next step reads it after B1
-        }
-        ST_STAMP(11);
-    }
-
-    if constexpr (DO_L) {
-        // a spawn without a preview takes the draw wave's first draw (rare)
+    {
         const bool need1 = draw && !pv_ok(mt0);
         if (__ballot(need1)) {
             lds_flag_wait(&sm.f2, (uint32_t)t + 1u);
@@ -1779,7 +1862,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
         uint32_t pw_out = pack_piece(id, rot, ax, ay, lock);
         if (draw) pw_out = pack_piece(sid, 0, W / 2, 0, lock);
         if (spawn) {
-            odesc = tab(sid * 4);
+            odesc = wc.tab(sid * 4);
             oax = W / 2;
             oay = 0;
         }
@@ -1818,7 +1901,7 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
             time = score = lines = holes = height = 0;
         }
         // st_step stores only the counter rows that changed (per env)
-        if constexpr (STEP2) {
+        if constexpr (KSTEPS == 1) {
             // st_step: straight from the registers, one coalesced dword per
             // lane and changed row (no staging through LDS at the end of the
             // chain), unconditional stores with an out-of-range offset
@@ -1849,33 +1932,30 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
                 };
                 inf(ST_STAT_TIME, time);
                 inf(kPieceRow, (int32_t)pw_out);
-                inf(ST_STAT_SCORE, locknow ? score : (int32_t)ss(ST_STAT_SCORE));
-                inf(ST_STAT_LINES, locknow ? lines : (int32_t)ss(ST_STAT_LINES));
-                inf(ST_STAT_HOLES, locknow ? holes : (int32_t)ss(ST_STAT_HOLES));
-                inf(ST_STAT_PIECE_HEIGHT, locknow ? height : (int32_t)ss(ST_STAT_PIECE_HEIGHT));
-                inf(ST_STAT_DEATHS, locknow ? deaths : (int32_t)ss(ST_STAT_DEATHS));
+                inf(ST_STAT_SCORE, locknow ? score : (int32_t)wc.ss(ST_STAT_SCORE));
+                inf(ST_STAT_LINES, locknow ? lines : (int32_t)wc.ss(ST_STAT_LINES));
+                inf(ST_STAT_HOLES, locknow ? holes : (int32_t)wc.ss(ST_STAT_HOLES));
+                inf(ST_STAT_PIECE_HEIGHT, locknow ? height : (int32_t)wc.ss(ST_STAT_PIECE_HEIGHT));
+                inf(ST_STAT_DEATHS, locknow ? deaths : (int32_t)wc.ss(ST_STAT_DEATHS));
                 inf(ST_STAT_EP_TIME, ep_t);
                 inf(ST_STAT_EP_SCORE, ep_s);
                 inf(ST_STAT_EP_LINES, ep_l);
                 inf(ST_STAT_EP_HOLES, ep_h);
             }
         } else {
-            ss(ST_STAT_TIME) = (uint32_t)time;
-            ss(kPieceRow) = pw_out;
+            wc.ss(ST_STAT_TIME) = (uint32_t)time;
+            wc.ss(kPieceRow) = pw_out;
             if (locknow) {
-                auto put = [&](int r, int32_t v, int32_t) { ss(r) = (uint32_t)v; };
-                put(ST_STAT_SCORE, score, o_score);
-                put(ST_STAT_LINES, lines, o_lines);
-                put(ST_STAT_HOLES, holes, o_holes);
-                put(ST_STAT_PIECE_HEIGHT, height, o_height);
-                put(ST_STAT_DEATHS, deaths, o_deaths);
+                wc.ss(ST_STAT_SCORE) = (uint32_t)score;
+                wc.ss(ST_STAT_LINES) = (uint32_t)lines;
+                wc.ss(ST_STAT_HOLES) = (uint32_t)holes;
+                wc.ss(ST_STAT_PIECE_HEIGHT) = (uint32_t)height;
+                wc.ss(ST_STAT_DEATHS) = (uint32_t)deaths;
             }
         }
 
         // ---- observation (tetris_env.py:301-302): board + current piece ----
-        if constexpr (KSTEPS != 1) {
-            if (KSTEPS != 1 || spawn) paint_box<S32>(L, lane, odesc.x, odesc.y, oax, oay, hmask);
-        }
+        if constexpr (KSTEPS != 1) paint_box<S32>(L, lane, odesc.x, odesc.y, oax, oay, hmask);
         wave_sync();
         const bool wide_obs = (p.n & 3) == 0 && e0 + kWave <= p.n &&
                               (reinterpret_cast<uintptr_t>(p.obs) & 15u) == 0 &&
@@ -2015,88 +2095,200 @@ __device__ __forceinline__ void run_steps(const KParams &p, StepLds<WT, F32, KST
     }
     }  // for t
     wave_sync();
-    if constexpr (ACT) {
-        // st_set_action_flag's sticky word: only lanes that saw a bad action
-        // store (a raw buffer store with an out-of-range offset elsewhere, no
-        // branch); a null flag has an empty range, so nothing is written
-        __builtin_amdgcn_raw_buffer_store_b32(1u, buf_rsrc(p.act_flag, 4u), bad_act ? 0u : kOff, 0, 0);
+    // st_set_action_flag's sticky word: only lanes that saw a bad action
+    // store (a raw buffer store with an out-of-range offset elsewhere, no
+    // branch); a null flag has an empty range, so nothing is written
+    __builtin_amdgcn_raw_buffer_store_b32(1u, buf_rsrc(p.act_flag, 4u), bad_act ? 0u : kOff, 0, 0);
+    if constexpr (KSTEPS != 1) {
+        BoardRows<WT>::template store<true>(p, L, wc, W, hmask);
+        // (st_step stored its changed rows per lane above)
+        store_staged_rows<false>(p, wc);
     }
-    if constexpr (KSTEPS != 1 && DO_L) {
-        // 32-bit buffer offsets: 64-bit row offsets shared with the prologue
-        // would stay live (in SGPRs) across the step loop
-        const auto rb = buf_rsrc(p.board, (uint32_t)((W + 3) & ~3) * (uint32_t)sd * 4u);
-        const uint32_t boff = (uint32_t)e0 * 4u + loff * 4u;
-#pragma unroll
-        for (int q = 0; q < NBQ; ++q) {
-            if (WT || 4 * q < W) {  // rows >= W: padding rows of the allocation
-                uint4 v = *reinterpret_cast<const uint4 *>(&L[(4 * q + lrow + kPad) * kWave + lcc]);
-                v.x &= hmask;
-                v.y &= hmask;
-                v.z &= hmask;
-                v.w &= hmask;
-                buf_store16<kST>(rb, boff + (uint32_t)(4 * q) * (uint32_t)sd * 4u, v);
-            }
-        }
-    }
-    // rollout: the staged counter rows, each wave the rows it owns (logic:
-    // 0-5 and the piece row, draw: the shape counts and the MT word); st_step
-    // stored its changed rows per lane above
-    constexpr uint32_t kRowsD = ((1u << 7) - 1u) << ST_STAT_COUNT0 | 1u << ST_STAT_MT_INDEX;
-    constexpr uint32_t kOwn = ROLE == kRoleD ? kRowsD : ((1u << kHotRows) - 1u) & ~kRowsD;
-    const auto rs = buf_rsrc(p.stats, (uint32_t)kHotRows * (uint32_t)sd * 4u);
-    const uint32_t soff = (uint32_t)e0 * 4u + loff * 4u;
-#pragma unroll
-    for (int q = 0; q < kHotQ; ++q) {
-        if constexpr (STEP2) break;
-        // row 15 (ep_time) is never staged: it is stored per lane on a reset
-        if (((kOwn >> (4 * q)) & 0xFu) == 0u) continue;
-        const bool st = (kOwn >> (4 * q + lrow)) & 1u;
-        buf_store16<kST>(rs, st ? soff + (uint32_t)(4 * q) * (uint32_t)sd * 4u : kOff,
-                         *reinterpret_cast<const uint4 *>(&SS[(4 * q + lrow) * kWave + lcc]));
-    }
-    if constexpr (STAMP && KSTEPS != 1) {
-        // rollout stamp build: words [0, 16) of the workgroup's slot the
-        // logic wave's per-phase cycle totals (stamp index i), [16, 32) the
-        // draw wave's; word 12 / 28: s_memrealtime span, 13 / 29: steps
-        ST_STAMP(6);
-        uint64_t *slot = p.stamps + (int64_t)blockIdx.x * kStampWords + (ROLE == kRoleD ? 16 : 0);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 12; ++i) slot[i] = tacc[i];
-            slot[12] = __builtin_amdgcn_s_memrealtime() - rt0;
-            slot[13] = (uint64_t)K;
-        }
-    }
-    if constexpr (STAMP && KSTEPS == 1) {
-        // words [0, 16) of the workgroup's slot: the logic wave (stamps
-        // 0-9, realtime start/end, HW_ID, XCC_ID, draw kind); [16, 32): the
-        // draw wave (stamps 0-11, realtime start/end)
-        ST_STAMP(6);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        ST_STAMP(7);
-        uint64_t *slot = p.stamps + (int64_t)blockIdx.x * kStampWords + (ROLE == kRoleD ? 16 : 0);
-        if (lane == 0) {
-            if constexpr (ROLE == kRoleD) {
-#pragma unroll
-                for (int i = 0; i < 12; ++i) slot[i] = tstamp[i];
-                slot[12] = rt0;
-                slot[13] = __builtin_amdgcn_s_memrealtime();
-                slot[14] = draw_kind;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 10; ++i) slot[i] = tstamp[i];
-                slot[10] = rt0;
-                slot[11] = __builtin_amdgcn_s_memrealtime();
-                slot[12] = __builtin_amdgcn_s_getreg(0xF804);  // HW_ID
-                slot[13] = __builtin_amdgcn_s_getreg(0xF814);  // XCC_ID
-                slot[14] = tstamp[10];  // round 6: reward / done issued
-                slot[15] = tstamp[11];  // round 6: the store phase's LDS reads arrived
-            }
-        }
-    }
+    dump_stamps<STAMP, KSTEPS, false>(p, lane, K, tstamp, tacc, tlast, rt0, 0u);
 }
 
-// st_step: two waves per 64 envs (kRoleL, kRoleD), see run_steps.
+// The draw wave: MT words, the next-generation block, the piece draw.
+template <int WT, int HT, bool F32, bool STAMP, int KSTEPS, bool SC0, bool VEC = false>
+__device__ __forceinline__ void step_draw(const KParams &p, StepLds<WT, F32, KSTEPS> &sm) {
+    static_assert(!VEC || KSTEPS == 1, "VEC: st_step only");
+    [[maybe_unused]] uint64_t tstamp[12] = {};
+    [[maybe_unused]] uint32_t tacc[12] = {};  // rollout stamp build: per-phase cycle totals
+    [[maybe_unused]] uint64_t tlast = 0;
+    [[maybe_unused]] uint64_t draw_kind = 0;  // stamp build: 1 = a lane twisted, 2 = a draw ran past 8 words
+    const uint32_t kAblate = ablate_bits(p);
+    [[maybe_unused]] uint64_t rt0 = 0;
+    if constexpr (STAMP) {
+        rt0 = __builtin_amdgcn_s_memrealtime();
+        tlast = __builtin_amdgcn_s_memtime();
+    }
+    ST_STAMP(0);
+    const WaveCtx wc(p, sm);
+    const int lane = wc.lane;
+    const int64_t e0 = wc.e0, e = wc.e, sd = wc.sd;
+    const bool real = wc.real;
+
+    // ---- loads: counter groups 2-3 (count2 .. MT word, piece); LCL: the
+    // shape counts and the MT word only ----
+    // (ablation 1024: every wave's counter groups from the first workgroup's
+    // lines -- the counter rows' HBM reads gone, timing only)
+    const uint32_t *ssrc = reinterpret_cast<const uint32_t *>(p.stats) + ((kAblate & 1024u) ? 0 : e0);
+    constexpr bool LCL = KSTEPS == 1 && !VEC;  // late counters, see above
+    StagedRows<LCL, true> sq;
+    sq.load(wc, ssrc, kAblate);
+    const int K = KSTEPS ? KSTEPS : p.k;
+    const uint32_t gate_v = gate_load<VEC>(p);
+    // two waves: the draw wave builds the piece table (and the walls, and
+    // the f32 nibble table)
+    build_tables<WT, F32>(p, sm, lane);
+    sq.store(wc);
+    if (lane == 0) sm.f2 = 0u;
+    wg_barrier();  // B0: the staged state is complete
+    if (gate_shut<VEC>(p, gate_v)) return;
+    for (int t = 0; t < K; ++t) {
+    // MT word at the start of the step
+    const uint32_t mt0 = wc.ss(ST_STAT_MT_INDEX);
+    if constexpr (STAMP && KSTEPS == 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    ST_STAMP(1);
+    ST_STAMP(2);
+    // the draw wave's next-generation chunk of this step: operands issued
+    // before B1, so they arrive while it waits for the lock decision
+    MtChunk chunk;
+    // ... and the count-dependent part of the preview draw (in st_step while
+    // the draw wave waits for the lock decision): a lane that draws spawns its
+    // preview first, so its draw sees the counts now + that shape (lanes
+    // without a valid preview redo this after their first draw, below)
+    int32_t cnt[7];
+    const MtRes mrs = mt_res(p.mt + e0 * kMtPitch, lane);
+    mt_chunk_issue(mrs, mt0, real && !(kAblate & (2u | 1048576u)), lane, chunk);  // (1048576: no chunks, timing only)
+    const int s0 = pv_id(mt0);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) cnt[i] = (int32_t)wc.ss(ST_STAT_COUNT0 + i) + (i == s0);  // _new_piece :199
+    int32_t csid = cnt[0];  // the spawned shape's count after the spawn
+#pragma unroll
+    for (int i = 1; i < 7; ++i) csid = s0 == i ? cnt[i] : csid;
+    DrawPar dpar = draw_par(cnt);
+    wg_barrier();  // B1: the draw wave learns which lanes lock
+    ST_STAMP(10);
+    __builtin_amdgcn_s_setprio(kDrawPrio);
+    const uint32_t lw = lane < 32 ? sm.lockm[t & 1][0] : sm.lockm[t & 1][1];
+    const bool locknow = (lw >> (lane & 31)) & 1u;
+
+    // ---------------- draw: MT window, issued now ----------------
+    // Every locking lane draws (its next preview, or -- without a valid
+    // preview -- its piece first); the window is consumed right away.
+    uint32_t mtst = mt0;  // packed (mt_pack + preview bits)
+    const bool want_pre = locknow && !(kAblate & 2u);
+    constexpr int kWin = KSTEPS == 1 ? 8 : 16;
+    MtPre pre;
+    // (ablation 524288: the window's words read as zeros, no traffic -- timing only)
+    mt_pre_load<kWin>(mrs, mtst, want_pre && !(kAblate & 524288u), pre);
+    ST_STAMP(3);
+
+    ST_STAMP(8);  // (stamp 8: between the early stores and the draw)
+    // ---------------- draw (tetris_env.py:183-199, :299 _new_piece, :306-315 clear) ----------------
+    // spawn id: the preview; lanes without one draw their piece first
+    int sid = pv_id(mt0);
+    {
+        // speculative in the draw wave (it does not know yet which locking
+        // lanes die without auto-reset): committed below only where `draw`
+        const bool dr_spec = locknow;
+        if constexpr (STAMP) {  // diagnostic split of the draw: MT-word wait | compute
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            ST_STAMP(9);
+        }
+        [[maybe_unused]] const uint32_t mt_before = mtst;
+        uint32_t mt_new = mtst;
+        if (!(kAblate & 2u)) {
+            mt_win_consume<kWin>(pre);
+            const bool need1 = dr_spec && !pv_ok(mt0);
+            if (__ballot(need1)) {  // rare: after st_seed / st_mt_sync / a host-written state
+                // the piece first, with the counts before the spawn
+                int32_t c0[7];
+#pragma unroll
+                for (int i = 0; i < 7; ++i) c0[i] = (int32_t)wc.ss(ST_STAT_COUNT0 + i);
+                const int pk = draw_shape<kWin, false>(need1, c0, mtst, p.mt + e0 * kMtPitch, sm.S, lane, pre, false);
+                if (need1) {
+                    sid = pk;
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) cnt[i] = c0[i] + (i == pk);  // _new_piece :199
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) csid = pk == i ? cnt[i] : csid;
+                }
+                dpar = draw_par(cnt);
+            }
+            sm.pick1[lane] = (uint32_t)sid;
+            if (lane == 0) lds_flag_set(&sm.f2, (uint32_t)t + 1u);
+            const uint32_t m0 = mtst;
+            const int npv = draw_core<kWin>(dr_spec, dpar, mtst, p.mt + e0 * kMtPitch, sm.S, lane, pre,
+                                            want_pre && pv_ok(mt0));
+            mt_new = pv_pack(mtst, npv, mt_consumed(m0, mtst));
+        } else {
+            sm.pick1[lane] = (uint32_t)sid;
+            if (lane == 0) lds_flag_set(&sm.f2, (uint32_t)t + 1u);
+        }
+        // this step's next-generation chunk (its operands arrived long ago);
+        // its env's progress advances unless that env's own draw switched
+        // generations (finishing the successor itself: same words)
+        const int chunk_pg = mt_chunk_store<KSTEPS == 1 ? kST : 0>(mrs, lane, chunk);
+        const bool chunk_me = lane == chunk.l;
+        ST_STAMP(4);
+        if constexpr (STAMP) {  // 1: a draw started a generation, 2: a draw ran past its 8 words
+            const int i0 = (int)(mt_before & 0x3FFu), i1 = (int)(mt_new & 0x3FFu);
+            draw_kind = (__ballot(dr_spec && i1 < i0) ? 1u : 0u) | (__ballot(dr_spec && i1 >= i0 && i1 - i0 > 8) ? 2u : 0u);
+        }
+        // commit: lanes whose lock consumed the preview
+        bool dr = locknow;
+        if (p.autoreset != ST_AUTORESET_SAME_STEP) {
+            lds_flag_wait(&sm.f1, (uint32_t)t + 1u);
+            const uint32_t w = lane < 32 ? sm.drawm[0] : sm.drawm[1];
+            dr = (w >> (lane & 31)) & 1u;
+        }
+        // (a lane that locks but does not draw -- a death without auto-reset
+        // -- keeps its old MT word: its speculative draw is dropped)
+        uint32_t mt_out = dr ? mt_new : mt0;
+        if (chunk_me && (mt_out & (1u << 20)) == (mt0 & (1u << 20))) {
+            int i2, pg2, c2;
+            mt_unpack(mt_out, i2, pg2, c2);
+            mt_out = mt_keep(mt_out, mt_pack(i2, chunk_pg, c2));
+        }
+        if constexpr (KSTEPS == 1) {
+            // st_step: this wave's changed counter rows straight from the
+            // registers, one coalesced dword per lane and row (no staging
+            // through LDS at the end of the chain): the MT word, and the
+            // count of the spawned shape (csid, counted above)
+            const auto rs = buf_rsrc(p.stats, (uint32_t)kHotRows * (uint32_t)sd * 4u);
+            const uint32_t eo = (uint32_t)e * 4u;
+            // (ablation 2048: the lock-path counter stores dropped, timing only)
+            const bool cst = !(kAblate & (2048u | 32768u));
+            const bool mst = cst && !(kAblate & 131072u) && (dr || chunk_me);
+            const bool kst = cst && !(kAblate & 65536u) && dr;
+            __builtin_amdgcn_raw_buffer_store_b32(mt_out, rs, mst ? eo + (uint32_t)ST_STAT_MT_INDEX * (uint32_t)sd * 4u : kOff,
+                                                  0, kST);
+            __builtin_amdgcn_raw_buffer_store_b32(
+                (uint32_t)csid, rs, kst ? eo + (uint32_t)(ST_STAT_COUNT0 + sid) * (uint32_t)sd * 4u : kOff, 0, kST);
+            if constexpr (VEC) {  // st_step_vec's info snapshot: the shape counts after the step
+                const auto ri = buf_rsrc(p.info, (uint32_t)ST_NSTAT * (uint32_t)p.n * 4u);
+#pragma unroll
+                for (int i = 0; i < 7; ++i)
+                    __builtin_amdgcn_raw_buffer_store_b32(
+                        (uint32_t)(dr ? cnt[i] : (int32_t)wc.ss(ST_STAT_COUNT0 + i)), ri,
+                        real ? ((uint32_t)(ST_STAT_COUNT0 + i) * (uint32_t)p.n + (uint32_t)e) * 4u : kOff, 0, kNT);
+            }
+        } else {
+            // rollout: the staged rows (stored at the end of the launch)
+            if (dr || chunk_me) wc.ss(ST_STAT_MT_INDEX) = mt_out;
+            if (dr) atomicAdd(&wc.ss(ST_STAT_COUNT0 + sid), 1u);  // shape_counts[name] += 1, :199 (ds_add, no return)
+            sm.mtw[t & 1][lane] = mt_out;  // the logic wave's next step reads it after B1
+        }
+        ST_STAMP(11);
+    }
+    }  // for t
+    wave_sync();
+    if constexpr (KSTEPS != 1) store_staged_rows<true>(p, wc);
+    dump_stamps<STAMP, KSTEPS, true>(p, lane, K, tstamp, tacc, tlast, rt0, draw_kind);
+}
+
+// st_step: two waves per 64 envs, see step_logic / step_draw.
 // What the prologue's first loads address -- the state and action
 // pointers, the row stride, the env count -- comes as six leading scalar
 // arguments, preloaded into SGPRs at wave launch (gfx950 kernarg preload:
@@ -2117,8 +2309,8 @@ __global__ __launch_bounds__(2 * kWave) void k_step(uint32_t *board, int32_t *st
     p.stride = stride;
     p.n = n;
     __shared__ StepLds<WT, F32, 1> sm;
-    if (threadIdx.x < kWave) run_steps<WT, HT, F32, STAMP, 1, SC0, kRoleL, VEC>(p, sm);
-    else run_steps<WT, HT, F32, STAMP, 1, SC0, kRoleD, VEC>(p, sm);
+    if (threadIdx.x < kWave) step_logic<WT, HT, F32, STAMP, 1, SC0, VEC>(p, sm);
+    else step_draw<WT, HT, F32, STAMP, 1, SC0, VEC>(p, sm);
 }
 
 // ---------------------------------------------------------------- rollout
@@ -2162,7 +2354,7 @@ __global__ __launch_bounds__(2 * kWave) void k_step(uint32_t *board, int32_t *st
 // rule is unchanged.  The next-generation chunk is built only for envs whose
 // reference state (before q0's draw) is in the generation q1 ended in, so it
 // never overwrites words a committed preview may give back.
-constexpr int kRoleO = 3;
+constexpr int kRoleL = 1, kRoleD = 2, kRoleO = 3;  // rollout_wave's roles
 // issue priority of the rollout's logic wave (its chain sets the step: 3
 // against 0, -6% per step; logic 0-3 x draw 0-2 measured in round 3,
 // profiles/r03/ro_ab_priorities.txt); the draw wave runs at kDrawPrio after
@@ -2204,12 +2396,8 @@ __device__ __forceinline__ void rollout_wave(const KParams &p, RoLds<WT, F32> &s
     // (it idles most of a step), by the draw wave with float32 obs (the
     // output wave's stores set that step)
     constexpr bool CHO = !F32;
-    const uint32_t kFlags = SC0 ? (p.flags & (ST_REWARD_STEP | ST_STEP_RESET)) : p.flags;
-#if defined(ST_ABLATION) && ST_ABLATION
-    const uint32_t kAblate = p.ablate;
-#else
-    constexpr uint32_t kAblate = 0u;
-#endif
+    const uint32_t kFlags = step_flags<SC0>(p);
+    const uint32_t kAblate = ablate_bits(p);
     // diagnostic build: per-phase cycle totals over the launch (stamp index i
     // = the phase that ends there), words [16 * role, 16 * role + 12) of the
     // workgroup's slot, + s_memrealtime span and the step count
@@ -2230,90 +2418,34 @@ __device__ __forceinline__ void rollout_wave(const KParams &p, RoLds<WT, F32> &s
     }
     uint32_t *const L = sm.L;
     uint32_t *const OV = sm.OV;
-    uint32_t *const SS = sm.SS;
-    const int W = WT ? WT : p.W;
-    const int H = HT ? HT : p.H;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t e0 = (int64_t)blockIdx.x * kWave;
-    const int64_t e = e0 + lane;
-    const int64_t sd = p.stride;
-    const bool real = e < p.n;
-    const uint32_t hmask = (1u << H) - 1u;
-    const uint32_t floorb = ~hmask;
+    const int W = WT ? WT : p.W, H = HT ? HT : p.H;
+    const uint32_t hmask = (1u << H) - 1u, floorb = ~hmask;
+    const WaveCtx wc(p, sm);
+    const int lane = wc.lane, lrow = wc.lrow, lcc = wc.lcc;
+    const int64_t e0 = wc.e0, e = wc.e, sd = wc.sd;
+    const bool real = wc.real;
     const int K = p.k;
-    const int lrow = lane >> 4, lcc = 4 * (lane & 15);  // transposed 16-B slot: row-in-group, env
     constexpr int NBQ = ((WT ? WT : kMaxW) + 3) / 4;
-    const uint32_t loff = (uint32_t)lrow * (uint32_t)sd + 4u * (uint32_t)(lane & 15);
-    auto clamp_off = [&](int q, int nrows) -> uint32_t {
-        const int r = 4 * q + lrow < nrows ? lrow : nrows - 1 - 4 * q;
-        return (uint32_t)r * (uint32_t)sd + 4u * (uint32_t)(lane & 15);
-    };
-    auto ss = [&](int r) -> uint32_t & { return SS[r * kWave + lane]; };
-    auto tab = [&](int i) -> uint2 { return *reinterpret_cast<const uint2 *>(&sm.T2[2 * i]); };
     auto col = [&](uint32_t *P, int x) -> uint32_t & { return P[(x + kPad) * kWave + lane]; };
 
     // ---- prologue: state into LDS (16 B per lane, transposed), B0 ----
     // logic: board + counter groups 0-1 (time .. count1); draw: counter
     // groups 2-3 (count2 .. MT word, piece), the walls, the piece table;
     // output: the zeroed overlay plane
-    const uint32_t *bsrc = p.board + e0;
-    const uint32_t *ssrc = reinterpret_cast<const uint32_t *>(p.stats) + e0;
+    [[maybe_unused]] const uint32_t *ssrc = reinterpret_cast<const uint32_t *>(p.stats) + e0;
     if constexpr (ROLE == kRoleL) {
-        uint4 bv[NBQ], sv[2];
-#pragma unroll
-        for (int q = 0; q < NBQ; ++q)
-            if (WT || 4 * q < W)
-                bv[q] = *reinterpret_cast<const uint4 *>(bsrc + (size_t)(4 * q) * sd +
-                                                         (4 * q + 4 <= W ? loff : clamp_off(q, W)));
-#pragma unroll
-        for (int q = 0; q < 2; ++q) sv[q] = *reinterpret_cast<const uint4 *>(ssrc + (size_t)(4 * q) * sd + loff);
-#pragma unroll
-        for (int q = 0; q < NBQ; ++q) {
-            if (WT || 4 * q < W) {
-                uint4 v = bv[q];
-                v.x |= floorb;
-                v.y |= floorb;
-                v.z |= floorb;
-                v.w |= floorb;
-                // rows >= W (allocation padding) are not staged (the draw
-                // wave writes the wall columns in the same prologue)
-                if (4 * q + lrow < W) *reinterpret_cast<uint4 *>(&L[(4 * q + lrow + kPad) * kWave + lcc]) = v;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) *reinterpret_cast<uint4 *>(&SS[(4 * q + lrow) * kWave + lcc]) = sv[q];
+        BoardRows<WT> br;
+        br.load(p.board + e0, wc, W);
+        StagedRows<false, false> sq;
+        sq.load(wc, ssrc, 0u);
+        br.template stage<false>(L, nullptr, wc, W, floorb);
+        sq.store(wc);
         if (lane == 0) sm.fo = 0u;
     } else if constexpr (ROLE == kRoleD) {
-        uint4 sv[2];
-#pragma unroll
-        for (int q = 2; q < kHotQ; ++q)
-            sv[q - 2] = *reinterpret_cast<const uint4 *>(ssrc + (size_t)(4 * q) * sd +
-                                                         (4 * q + 4 <= kHotRows ? loff : clamp_off(q, kHotRows)));
-        uint32_t tab_m = 0, tab_g = 0;
-#pragma unroll
-        for (int i = 0; i < 28; ++i) {
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(tab_m) : "s"(kBox.m[i]), "i"(i));
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(tab_g) : "s"(kBox.g[i]), "i"(i));
-        }
-#pragma unroll
-        for (int x = 0; x < kPad; ++x) {
-            L[x * kWave + lane] = ~0u;
-            L[(W + kPad + x) * kWave + lane] = ~0u;
-        }
-        if (lane < 28) {
-            sm.T2[2 * lane] = tab_m;
-            sm.T2[2 * lane + 1] = tab_g;
-        }
-        if constexpr (F32) {
-            if (lane < 16) {
-                sm.F4[4 * lane] = (float)(lane & 1);
-                sm.F4[4 * lane + 1] = (float)((lane >> 1) & 1);
-                sm.F4[4 * lane + 2] = (float)((lane >> 2) & 1);
-                sm.F4[4 * lane + 3] = (float)((lane >> 3) & 1);
-            }
-        }
-#pragma unroll
-        for (int q = 2; q < kHotQ; ++q) *reinterpret_cast<uint4 *>(&SS[(4 * q + lrow) * kWave + lcc]) = sv[q - 2];
+        StagedRows<false, true> sq;
+        sq.load(wc, ssrc, 0u);
+        build_tables<WT, F32>(p, sm, lane);
+        sq.store(wc);
         if (lane == 0) {
             sm.fl = 0u;
             sm.fd = 0u;
@@ -2330,14 +2462,14 @@ __device__ __forceinline__ void rollout_wave(const KParams &p, RoLds<WT, F32> &s
 
     if constexpr (ROLE == kRoleL) {
         // ================================================================ logic
-        uint32_t pw = ss(kPieceRow);
-        int32_t time = (int32_t)ss(ST_STAT_TIME);
-        int32_t score = (int32_t)ss(ST_STAT_SCORE), lines = (int32_t)ss(ST_STAT_LINES);
-        int32_t holes = (int32_t)ss(ST_STAT_HOLES), height = (int32_t)ss(ST_STAT_PIECE_HEIGHT);
-        int32_t deaths = (int32_t)ss(ST_STAT_DEATHS);
+        uint32_t pw = wc.ss(kPieceRow);
+        int32_t time = (int32_t)wc.ss(ST_STAT_TIME);
+        int32_t score = (int32_t)wc.ss(ST_STAT_SCORE), lines = (int32_t)wc.ss(ST_STAT_LINES);
+        int32_t holes = (int32_t)wc.ss(ST_STAT_HOLES), height = (int32_t)wc.ss(ST_STAT_PIECE_HEIGHT);
+        int32_t deaths = (int32_t)wc.ss(ST_STAT_DEATHS);
         uint2 d4[4];  // the current piece's four rotations
 #pragma unroll
-        for (int r = 0; r < 4; ++r) d4[r] = tab((int)(pw & 7u) * 4 + r);
+        for (int r = 0; r < 4; ++r) d4[r] = wc.tab((int)(pw & 7u) * 4 + r);
         bool bad_act = false;
         // LAZYH (fixed width): holes is counted when read -- a death, a holes
         // reward, the epilogue -- not at every lock (the board changes only
@@ -2370,16 +2502,14 @@ __device__ __forceinline__ void rollout_wave(const KParams &p, RoLds<WT, F32> &s
             int ay = pay;
             int lock = plock;
             stamp(1);
-            // ---- action (tetris_env.py:245; value_action_map :152-160) + drop ----
+            // ---- action + drop, gravity + lock delay (move_cand, move_resolve) ----
             // both descriptors from registers: the columns are one LDS round trip
-            const bool tries = act == 0u || act == 1u || act == 4u || act == 5u;
-            const int cx = ax + (act == 0u ? -1 : (act == 1u ? 1 : 0));
-            const int cr = (rot + (act == 4u ? 1 : 0) + (act == 5u ? 3 : 0)) & 3;  // (selects: the ternary chain became an exec-mask branch)
+            const MoveCand mc = move_cand(act, ax, rot);
             uint2 desc = pdesc;
-            const uint2 cdesc = sel4(d4, cr);
+            const uint2 cdesc = sel4(d4, mc.cr);
             uint32_t cur[4], cand[4];
             read_box(L, lane, desc.y, ax, cur);
-            read_box(L, lane, cdesc.y, cx, cand);
+            read_box(L, lane, cdesc.y, mc.cx, cand);
             // the queue / planes hand-off, read optimistically in the same
             // LDS round trip as the columns: both counters, step t + 1's
             // action and the queue word; taken after the action phase if
@@ -2392,35 +2522,9 @@ __device__ __forceinline__ void rollout_wave(const KParams &p, RoLds<WT, F32> &s
             const uint32_t act_n0 = lds_ld(&sm.act[(t + 1) & 3][lane]);
             const uint32_t qwd0 = lds_ld(&sm.qring[lane]);
             __atomic_signal_fence(__ATOMIC_SEQ_CST);
-            const bool ok = tries && !collides_v<S32>(cdesc.x, ay, cand);
-            ax = ok ? cx : ax;
-            rot = ok ? cr : rot;
-            desc.x = ok ? cdesc.x : desc.x;
-            desc.y = ok ? cdesc.y : desc.y;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) cur[j] = ok ? cand[j] : cur[j];
-            int d = drop_box(desc.y, ay, cur);
-            if (act == 2u) {                  // hard_drop :54-59
-                ay += d;
-                d = 0;
-            } else if (act == 3u && d > 0) {  // soft_drop :49-51
-                ay += 1;
-                d -= 1;
-            }
-            // ---- gravity + lock delay (tetris_env.py:247-262) ----
-            if (d > 0) {
-                ay += 1;
-                d -= 1;
-                if (kFlags & ST_STEP_RESET) lock = 0;
-            }
-            time += 1;
-            int32_t rew = (kFlags & ST_REWARD_STEP) ? 1 : 0;
-            bool locknow = false;
-            if (d == 0) {
-                const int l1 = lock + 1;
-                lock = lock_next(l1, p.lock_mod);
-                locknow = lock == 0 && !(kAblate & 1u);
-            }
+            int32_t rew = 0;
+            const bool locknow = move_resolve<S32>(act, mc, cdesc, cand, desc, cur, rot, ax, ay, lock, time, rew,
+                                                   kFlags, kAblate, p.lock_mod);
             stamp(2);
             // the next spawn's piece (drawn by round t - 2 at the latest; the
             // two initial draws count as one round) and its descriptors, for a
@@ -2452,134 +2556,24 @@ __device__ __forceinline__ void rollout_wave(const KParams &p, RoLds<WT, F32> &s
             const int sid = (int)((qwd >> (4u * (nq & 3u))) & 7u);
             uint2 s4[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) s4[r] = tab(sid * 4 + r);
+            for (int r = 0; r < 4; ++r) s4[r] = wc.tab(sid * 4 + r);
             stamp(3);
 
             // ---- lock path (tetris_env.py:263-299) ----
             bool died = false, spawn = false;
-            [[maybe_unused]] uint32_t tb[WT ? WT : 1];  // the board after the lock (a reset copies it to OV)
+            LockCols<WT> lb;  // (cw: the board after the lock; a reset copies it to OV)
             if (locknow) {
-                paint_box<S32>(L, lane, desc.x, desc.y, ax, ay, hmask);
-                uint32_t andv = ~0u, orv = 0, sctz = 0, spop = 0;
-                if constexpr (WT != 0) {
-                    // all column reads before any use: one LDS round trip (see
-                    // run_steps' lock path)
-#pragma unroll
-                    for (int x = 0; x < WT; ++x) tb[x] = col(L, x);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int x = 0; x < WT; ++x) {
-                        const uint32_t v = tb[x];
-                        andv &= v;
-                        orv |= v;
-                        if constexpr (!LAZYH) {
-                            sctz += __builtin_ctz(v);
-                            spop += __builtin_popcount(v);
-                        }
-                    }
-                } else {
-#pragma unroll 8
-                    for (int x = 0; x < W; ++x) {
-                        const uint32_t v = col(L, x);
-                        andv &= v;
-                        orv |= v;
-                        sctz += __builtin_ctz(v);
-                        spop += __builtin_popcount(v);
-                    }
-                }
-                andv &= hmask;
-                int32_t ncl = 0;
-                if (andv) {  // full rows: compact, recount (_clear_lines :205-216)
-                    ncl = __builtin_popcount(andv);
-                    orv = 0;
-                    sctz = spop = 0;
-                    if constexpr (WT != 0) {
-                        uint32_t c[WT];
-#pragma unroll
-                        for (int x = 0; x < WT; ++x) c[x] = tb[x] & hmask;
-                        uint32_t full = andv;
-                        while (full) {
-                            const int r = __builtin_ctz(full);
-                            full &= full - 1u;
-                            const uint32_t above = (1u << r) - 1u;
-                            const uint32_t keep = ~(above | (1u << r));
-#pragma unroll
-                            for (int x = 0; x < WT; ++x) c[x] = (c[x] & keep) | ((c[x] & above) << 1);
-                        }
-#pragma unroll
-                        for (int x = 0; x < WT; ++x) {
-                            const uint32_t v = c[x] | floorb;
-                            tb[x] = v;
-                            col(L, x) = v;
-                            orv |= v;
-                            if constexpr (!LAZYH) {
-                                sctz += __builtin_ctz(v);
-                                spop += __builtin_popcount(v);
-                            }
-                        }
-                    } else {
-#pragma unroll 8
-                        for (int x = 0; x < W; ++x) {
-                            const uint32_t v = compact(col(L, x) & hmask, andv) | floorb;
-                            col(L, x) = v;
-                            orv |= v;
-                            sctz += __builtin_ctz(v);
-                            spop += __builtin_popcount(v);
-                        }
-                    }
-                    lines += ncl;
-                }
-                orv &= hmask;
-                // _count_holes :218-220 (LAZYH: from tb where it is needed)
+                lock_board<WT, S32, !LAZYH>(L, lane, W, hmask, floorb, desc, ax, ay, lb);
+                // _count_holes :218-220 (LAZYH: from the column words where it is needed)
                 const auto count_holes = [&]() -> int32_t {
-                    if constexpr (LAZYH) {
-                        uint32_t hc = 0, hp = 0;
-#pragma unroll
-                        for (int x = 0; x < (WT ? WT : 1); ++x) {
-                            hc += __builtin_ctz(tb[x]);
-                            hp += __builtin_popcount(tb[x]);
-                        }
-                        sctz = hc;
-                        spop = hp;
-                    }
-                    return W * H - (int32_t)sctz - ((int32_t)spop - W * (32 - H));
+                    if constexpr (LAZYH) hole_sums(lb.cw, lb.sctz, lb.spop);
+                    return holes_of(lb.sctz, lb.spop, W, H);
                 };
-                if (kFlags & ST_ADVANCED_CLEARS) {  // :266-269
-                    constexpr uint64_t kClr = (40ull << 12) | (100ull << 24) | (300ull << 36) | (1200ull << 48);
-                    const int32_t sc = ncl <= 4 ? (int32_t)((kClr >> (12 * ncl)) & 0xFFFu) : 0;
-                    rew += (sc * 5) / 2;
-                    score += sc;
-                } else if (kFlags & ST_HIGH_SCORING) {  // :270-272
-                    rew += 1000 * ncl;
-                    score += ncl;
-                } else {  // :273-275
-                    rew += 100 * ncl;
-                    score += ncl;
-                }
-                if (orv & 1u) {  // death :277-281
-                    holes = count_holes();
-                    hstale = false;
-                    deaths += 1;
-                    died = true;
-                    rew = -100;
-                } else {  // :283-299
-                    const int32_t old_holes = holes;
-                    // holes feeds the reward only under the two holes flags;
-                    // otherwise it is recounted from the board where it is
-                    // read next (a death, the epilogue)
-                    if (!LAZYH || (kFlags & (ST_PENALISE_HOLES | ST_PENALISE_HOLES_INCREASE))) holes = count_holes();
-                    else hstale = true;
-                    const int32_t hgt = __builtin_popcount(orv);
-                    if (kFlags & ST_PENALISE_HEIGHT) {
-                        rew -= hgt;
-                    } else if (kFlags & ST_PENALISE_HEIGHT_INCREASE) {
-                        if (hgt > height) rew -= 10 * (hgt - height);
-                        height = hgt;
-                    }
-                    if (kFlags & ST_PENALISE_HOLES) rew -= 5 * holes;
-                    else if (kFlags & ST_PENALISE_HOLES_INCREASE) rew -= 5 * (holes - old_holes);
-                    spawn = true;
-                }
+                const LockRes lr = lock_score<LAZYH>(kFlags, lb.ncl, lb.orv, count_holes, holes, height, rew, score,
+                                                     lines, holes, height, deaths);
+                died = lr.died;
+                spawn = lr.spawn;
+                hstale = lr.hlazy;
             }
             stamp(4);
             const bool reset_now = died && p.autoreset == ST_AUTORESET_SAME_STEP;
@@ -2618,7 +2612,7 @@ __device__ __forceinline__ void rollout_wave(const KParams &p, RoLds<WT, F32> &s
                 if constexpr (WT != 0) {
 #pragma unroll
                     for (int x = 0; x < WT; ++x) {
-                        col(OV, x) = tb[x] & hmask;
+                        col(OV, x) = lb.cw[x] & hmask;
                         col(L, x) = floorb;
                     }
                 } else {
@@ -2657,47 +2651,32 @@ __device__ __forceinline__ void rollout_wave(const KParams &p, RoLds<WT, F32> &s
         wg_barrier();  // the output wave has read the last step's planes
         // ---- epilogue: board and the rows this wave owns ----
         __builtin_amdgcn_raw_buffer_store_b32(1u, buf_rsrc(p.act_flag, 4u), bad_act ? 0u : kOff, 0, 0);
-        ss(ST_STAT_TIME) = (uint32_t)time;
-        ss(ST_STAT_SCORE) = (uint32_t)score;
-        ss(ST_STAT_LINES) = (uint32_t)lines;
+        wc.ss(ST_STAT_TIME) = (uint32_t)time;
+        wc.ss(ST_STAT_SCORE) = (uint32_t)score;
+        wc.ss(ST_STAT_LINES) = (uint32_t)lines;
         if constexpr (LAZYH) {
             if (hstale) {
-                uint32_t hc = 0, hp = 0;
+                uint32_t v[WT ? WT : 1], hc, hp;
 #pragma unroll
-                for (int x = 0; x < (WT ? WT : 1); ++x) {
-                    const uint32_t v = col(L, x);
-                    hc += __builtin_ctz(v);
-                    hp += __builtin_popcount(v);
-                }
-                holes = W * H - (int32_t)hc - ((int32_t)hp - W * (32 - H));
+                for (int x = 0; x < (WT ? WT : 1); ++x) v[x] = col(L, x);
+                hole_sums(v, hc, hp);
+                holes = holes_of(hc, hp, W, H);
             }
         }
-        ss(ST_STAT_HOLES) = (uint32_t)holes;
-        ss(ST_STAT_PIECE_HEIGHT) = (uint32_t)height;
-        ss(ST_STAT_DEATHS) = (uint32_t)deaths;
-        ss(kPieceRow) = pack_piece(pid, prot, pax, pay, plock);
+        wc.ss(ST_STAT_HOLES) = (uint32_t)holes;
+        wc.ss(ST_STAT_PIECE_HEIGHT) = (uint32_t)height;
+        wc.ss(ST_STAT_DEATHS) = (uint32_t)deaths;
+        wc.ss(kPieceRow) = pack_piece(pid, prot, pax, pay, plock);
         wave_sync();
-        const auto rb = buf_rsrc(p.board, (uint32_t)((W + 3) & ~3) * (uint32_t)sd * 4u);
-        const uint32_t boff = (uint32_t)e0 * 4u + loff * 4u;
-#pragma unroll
-        for (int q = 0; q < NBQ; ++q) {
-            if ((WT || 4 * q < W) && 4 * q + lrow < W) {
-                uint4 v = *reinterpret_cast<const uint4 *>(&L[(4 * q + lrow + kPad) * kWave + lcc]);
-                v.x &= hmask;
-                v.y &= hmask;
-                v.z &= hmask;
-                v.w &= hmask;
-                buf_store16<kST>(rb, boff + (uint32_t)(4 * q) * (uint32_t)sd * 4u, v);
-            }
-        }
+        BoardRows<WT>::template store<false>(p, L, wc, W, hmask);
     } else if constexpr (ROLE == kRoleD) {
         // ================================================================ draw
         uint32_t *const mtg = p.mt + e0 * kMtPitch;
         const MtRes mrs = mt_res(mtg, lane);
-        const uint32_t w0 = ss(ST_STAT_MT_INDEX);
+        const uint32_t w0 = wc.ss(ST_STAT_MT_INDEX);
         int32_t cnt_r[7];  // shape_counts (the spawned pieces only)
 #pragma unroll
-        for (int i = 0; i < 7; ++i) cnt_r[i] = (int32_t)ss(ST_STAT_COUNT0 + i);
+        for (int i = 0; i < 7; ++i) cnt_r[i] = (int32_t)wc.ss(ST_STAT_COUNT0 + i);
         // mtc: the committed state word (the queue head q0 as its preview, the
         // MT position after q0's draw); mta: the MT position after the last
         // queued draw (q1's), c1 the words that draw consumed
@@ -2884,8 +2863,8 @@ __device__ __forceinline__ void rollout_wave(const KParams &p, RoLds<WT, F32> &s
 #pragma unroll
         // the spawned pieces' counts = cq less the queue head's, which cq
         // already holds (cq = cnt_r + the head's count throughout the loop)
-        for (int i = 0; i < 7; ++i) ss(ST_STAT_COUNT0 + i) = (uint32_t)(cq[i] - (i == q0 ? 1 : 0));
-        ss(ST_STAT_MT_INDEX) = mtc;
+        for (int i = 0; i < 7; ++i) wc.ss(ST_STAT_COUNT0 + i) = (uint32_t)(cq[i] - (i == q0 ? 1 : 0));
+        wc.ss(ST_STAT_MT_INDEX) = mtc;
         wave_sync();
     } else {
         // ================================================================ output
@@ -3099,19 +3078,7 @@ __device__ __forceinline__ void rollout_wave(const KParams &p, RoLds<WT, F32> &s
     }
     // ---- counter rows this wave owns (logic: 0-5 and the piece row, draw:
     // the shape counts and the MT word) ----
-    if constexpr (ROLE != kRoleO) {
-        constexpr uint32_t kRowsD = ((1u << 7) - 1u) << ST_STAT_COUNT0 | 1u << ST_STAT_MT_INDEX;
-        constexpr uint32_t kOwn = ROLE == kRoleD ? kRowsD : ((1u << kHotRows) - 1u) & ~kRowsD;
-        const auto rs = buf_rsrc(p.stats, (uint32_t)kHotRows * (uint32_t)sd * 4u);
-        const uint32_t soff = (uint32_t)e0 * 4u + loff * 4u;
-#pragma unroll
-        for (int q = 0; q < kHotQ; ++q) {
-            if (((kOwn >> (4 * q)) & 0xFu) == 0u) continue;
-            const bool st = (kOwn >> (4 * q + lrow)) & 1u;
-            buf_store16<kST>(rs, st ? soff + (uint32_t)(4 * q) * (uint32_t)sd * 4u : kOff,
-                             *reinterpret_cast<const uint4 *>(&SS[(4 * q + lrow) * kWave + lcc]));
-        }
-    }
+    if constexpr (ROLE != kRoleO) store_staged_rows<ROLE == kRoleD>(p, wc);
     if constexpr (STAMP) {
         uint64_t *slot = p.stamps + (int64_t)blockIdx.x * kStampWords + 16 * (ROLE == kRoleL ? 0 : ROLE == kRoleD ? 1 : 2);
         if (lane == 0) {
@@ -3134,15 +3101,15 @@ __global__ __launch_bounds__(3 * kWave) void k_rollout(KParams p) {
     else rollout_wave<WT, HT, F32, SC0, STAMP, kRoleO>(p, sm);
 }
 
-// The two-wave rollout (run_steps, board and counters in LDS): launch_rollout
+// The two-wave rollout (step_logic / step_draw, board and counters in LDS): launch_rollout
 // takes it for batches of more than 4 workgroups per CU, where the three-wave
 // kernel's extra waves and window reloads cost more than its shorter logic
 // chain gains (131,072 envs: 2.8 against 4.0 us per step).
 template <int WT, int HT, bool F32, bool SC0 = false>
 __global__ __launch_bounds__(2 * kWave) void k_rollout2(KParams p) {
     __shared__ StepLds<WT, F32, 0> sm;
-    if (threadIdx.x < kWave) run_steps<WT, HT, F32, false, 0, SC0, kRoleL>(p, sm);
-    else run_steps<WT, HT, F32, false, 0, SC0, kRoleD>(p, sm);
+    if (threadIdx.x < kWave) step_logic<WT, HT, F32, false, 0, SC0>(p, sm);
+    else step_draw<WT, HT, F32, false, 0, SC0>(p, sm);
 }
 
 // no scoring flags (SC0 specializations of the 10x20 kernels)
@@ -3325,7 +3292,7 @@ __global__ __launch_bounds__(kWave) void k_render(KParams p) {
     }
     const uint32_t pw = p.piece[e];
     const uint32_t t = (pw & 7u) * 4 + ((pw >> 3) & 3u);
-    paint(L, lane, c_tab_m[t], c_tab_g[t], (int)((pw >> 5) & 63u), (int)((pw >> 11) & 63u), hmask);
+    paint_box(L, lane, c_tab_m[t], c_tab_g[t], (int)((pw >> 5) & 63u), (int)((pw >> 11) & 63u), hmask);
     if (e < p.n)
         for (int x = 0; x < W; ++x) p.obs[x * p.n + e] = lcol(L, x, lane) & hmask;
 }
@@ -3770,7 +3737,7 @@ __global__ __launch_bounds__(256) void k_gate_actions(const uint8_t *__restrict_
 // depends only on the board and the piece id.
 __global__ __launch_bounds__(kWave) void k_policy_greedy(KParams p, uint64_t seed, int64_t t,
                                                          uint32_t explore, uint8_t *out) {
-    constexpr int P = 8;  // wall columns each side: x + dx spans [-6, W + 5]
+    constexpr int P = 8;  // wall columns each side: the box's columns span [-6, W + 5]
     __shared__ uint32_t L[(kMaxW + 2 * P) * kWave];
     const int lane = threadIdx.x;
     const int64_t e = (int64_t)blockIdx.x * kWave + lane;
@@ -3789,26 +3756,27 @@ __global__ __launch_bounds__(kWave) void k_policy_greedy(KParams p, uint64_t see
     for (int r = 0; r < 4; ++r) {
         const uint32_t m = c_tab_m[id * 4 + r], g = c_tab_g[id * 4 + r];
         for (int x = -3; x < W + 3; ++x) {
+            const int x0 = box_x0(g, x);
             uint32_t v[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = col(x + pc_dx(g, j));
+            for (int j = 0; j < 4; ++j) v[j] = col(x0 + j);
             if (collides_v(m, 0, v)) continue;
-            const int y = drop_v(g, 0, v);
+            const int y = drop_box(g, 0, v);
             bool ok = true;
             uint32_t pb[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const uint32_t byte = (m >> (8 * j)) & 0xFFu;
-                ok = ok && y + __builtin_ctz(byte) - 3 >= 0;
+                ok = ok && (byte == 0u || y + __builtin_ctz(byte) - 3 >= 0);  // (a box column without cells)
                 pb[j] = pc_bits(m, j, y) & hmask;
             }
-            // the board with the piece: column c gets the bits of every
-            // descriptor column at c (repeated last columns are idempotent)
+            // the board with the piece: column c gets the bits of the box
+            // column at c
             uint32_t andv = hmask;
             for (int c = 0; c < W; ++c) {
                 uint32_t w = col(c);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) w |= x + pc_dx(g, j) == c ? pb[j] : 0u;
+                for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
                 andv &= w;
             }
             const int lines = __builtin_popcount(andv);
@@ -3817,7 +3785,7 @@ __global__ __launch_bounds__(kWave) void k_policy_greedy(KParams p, uint64_t see
             for (int c = 0; c < W; ++c) {
                 uint32_t w = col(c);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) w |= x + pc_dx(g, j) == c ? pb[j] : 0u;
+                for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
                 w = (andv ? compact(w & hmask, andv) : (w & hmask)) | floorb;
                 holes += H - (int)__builtin_ctz(w) - __builtin_popcount(w & hmask);
                 orv |= w & hmask;

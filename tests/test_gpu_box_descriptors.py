@@ -1,5 +1,6 @@
-"""Box-column piece descriptors in the one-launch-per-step kernels (run_steps:
-st_step, st_step_vec, st_step_wire, st_step_f32 and the two-wave rollout).
+"""Box-column piece descriptors in the one-launch-per-step kernels (step_logic
+and step_draw: st_step, st_step_vec, st_step_wire, st_step_f32 and the
+two-wave rollout) and the step rules they share with the three-wave rollout.
 
 A rotation is read, painted and erased as four consecutive board columns from
 its leftmost one, so a piece held against a wall reaches into the pad columns
@@ -246,4 +247,43 @@ def test_two_wave_rollout_equals_steps():
             assert np.array_equal(sa[k], sb[k]), k
     finally:
         a.close()
+        b.close()
+
+
+ROLLOUT_CASES = [((10, 20), "c3", "packed"), ((10, 20), "c4", "packed"), ((10, 20), "c3", "f32"),
+                 ((6, 9), "c3", "packed"), ((4, 4), "c3", "packed"), ((5, 27), "c3", "packed")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("board,scoring,obs", ROLLOUT_CASES, ids=lambda v: v if isinstance(v, str) else "%dx%d" % v)
+def test_three_wave_rollout_vs_oracle(board, scoring, obs):
+    """k_rollout (st_rollout up to 4 workgroups per CU: every n here) on the
+    wall pattern, the surface of the shared move / lock / scoring rules that
+    the step tests above do not reach.  T steps as four launches, so the state
+    is stored and reloaded and the piece queue restarts three times: obs,
+    reward and done of every step, and the final state."""
+    G = _engine()
+    W, H = board
+    n = BOARDS[board]
+    assert n <= 64 * 4 * torch.cuda.get_device_properties(0).multi_processor_count  # the three-wave kernel
+    ref = _ref(W, H, scoring)
+    b = G.TetrisBatch(n, width=W, height=H, autoreset="same_step", seeds=[SEED0 + e for e in range(n)],
+                      **(C4 if scoring == "c4" else {}))
+    b.reset()
+    try:
+        acts = torch.as_tensor(ref["acts"].copy(), device=b.device)
+        K = T // 4
+        for t0 in range(0, T, K):
+            o, rew, dn = b.rollout(acts[t0:t0 + K], obs=obs)
+            o, rew, dn = o.cpu().numpy(), rew.cpu().numpy(), dn.cpu().numpy()
+            for k in range(K):
+                t = t0 + k
+                assert np.array_equal(rew[k], ref["reward"][t]), ("reward", t)
+                assert np.array_equal(dn[k].astype(np.uint8), ref["done"][t]), ("done", t)
+                if obs == "f32":
+                    assert np.array_equal(o[k], _unpack_f32(ref["obs"][t], H)), ("f32 obs", t)
+                else:
+                    assert np.array_equal(o[k].view(np.uint32).T, ref["obs"][t]), ("obs", t)
+        _check_final_state(b, ref)
+    finally:
         b.close()
