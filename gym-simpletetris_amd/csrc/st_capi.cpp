@@ -522,14 +522,27 @@ int st_gate_actions(st_ctx *c, const uint8_t *d_actions, st_stream stream) {
     if (!c || !d_actions) return fail(ST_EINVAL, "st_gate_actions: null argument");
     DeviceGuard g(c->device);
     if (!c->gate) {  // first use: the gate words (k_gate_actions), the mapped host word, the event
-        ST_HIP(hipMalloc(&c->gate, 4 * sizeof(uint32_t)));
-        ST_HIP(hipMemset(c->gate, 0, 4 * sizeof(uint32_t)));
-        ST_HIP(hipHostMalloc(&c->gate_host, sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-        *c->gate_host = 0;
-        void *dp = nullptr;
-        ST_HIP(hipHostGetDevicePointer(&dp, c->gate_host, 0));
-        c->gate_host_dev = static_cast<uint32_t *>(dp);
-        ST_HIP(hipEventCreateWithFlags(&c->gate_ev, hipEventDisableTiming));
+        // into locals first: the context takes them only when every one
+        // succeeded (a later call never meets a half-built gate)
+        uint32_t *gate = nullptr, *host = nullptr;
+        void *host_dev = nullptr;
+        hipEvent_t ev = nullptr;
+        hipError_t e = hipMalloc(&gate, 4 * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(gate, 0, 4 * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipHostMalloc(&host, sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) e = hipHostGetDevicePointer(&host_dev, host, 0);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            if (ev) (void)hipEventDestroy(ev);
+            if (host) (void)hipHostFree(host);
+            if (gate) (void)hipFree(gate);
+            return hip_fail(e, "st_gate_actions: allocating the gate");
+        }
+        *host = 0;
+        c->gate = gate;
+        c->gate_host = host;
+        c->gate_host_dev = static_cast<uint32_t *>(host_dev);
+        c->gate_ev = ev;
     }
     c->gate_epoch = (c->gate_epoch + 1u) & 0x7FFFFFFFu ? (c->gate_epoch + 1u) & 0x7FFFFFFFu : 1u;  // 31 bits, never 0
     hipStream_t s = (hipStream_t)stream;

@@ -40,12 +40,6 @@ NSTAT = 19
 MT_N = 624
 EXPORT_MT, EXPORT_OBS_F32 = 1, 2  # st_export_env parts
 
-EXPORTS = ("st_create", "st_destroy", "st_seed", "st_reset", "st_step", "st_step_f32", "st_step_n", "st_step_vec", "st_rollout",
-           "st_wire_words", "st_step_wire", "st_unwire", "st_unwire_shards",
-           "st_obs_to_f32", "st_render", "st_grayscale", "st_state", "st_copy", "st_mt_sync", "st_state_bytes", "st_save",
-           "st_load", "st_export_env", "st_export_words", "st_check_actions", "st_set_action_flag", "st_gate_actions",
-           "st_gate_wait", "st_stream_sync", "st_host_device_ptr", "st_stream_wait", "st_gen_actions", "st_policy_greedy", "st_debug_stamps", "st_last_error", "st_abi_version")
-
 
 class StError(RuntimeError):
     """A C-ABI call returned a negative st_status."""
@@ -69,6 +63,49 @@ class StateViews(ctypes.Structure):
                 ("mt_pitch", ctypes.c_int64)]
 
 
+# every function of include/simpletetris.h: (argument types, result type)
+_vp, _i32, _i64, _u32, _u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64
+SIG = {
+    "st_create": ([ctypes.POINTER(_vp), ctypes.POINTER(Config), ctypes.c_int, _i64], ctypes.c_int),
+    "st_destroy": ([_vp], ctypes.c_int),
+    "st_seed": ([_vp, _vp, _vp], ctypes.c_int),
+    "st_reset": ([_vp, _vp, _vp], ctypes.c_int),
+    "st_step": ([_vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_step_f32": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_step_n": ([_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_step_vec": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_rollout": ([_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_wire_words": ([_i32, _i32], ctypes.c_int),
+    "st_step_wire": ([_vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_unwire": ([_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_unwire_shards": ([_i32, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_obs_to_f32": ([_vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_render": ([_vp, _vp, _vp], ctypes.c_int),
+    "st_grayscale": ([_vp, _vp, _i32, _i32, _i32, _vp, _vp], ctypes.c_int),
+    "st_state": ([_vp, ctypes.POINTER(StateViews)], ctypes.c_int),
+    "st_copy": ([_vp, _vp, _i64, _vp], ctypes.c_int),
+    "st_mt_sync": ([_vp, _vp], ctypes.c_int),
+    "st_state_bytes": ([_vp], _i64),
+    "st_save": ([_vp, _vp, _i64], ctypes.c_int),
+    "st_load": ([_vp, _vp, _i64], ctypes.c_int),
+    "st_export_env": ([_vp, _i64, _vp, _vp, _vp, _u32, _vp, _vp], ctypes.c_int),
+    "st_export_words": ([_i32, _i32], ctypes.c_int),
+    "st_check_actions": ([_vp, _i64, _vp, _vp], ctypes.c_int),
+    "st_set_action_flag": ([_vp, _vp], ctypes.c_int),
+    "st_gate_actions": ([_vp, _vp, _vp], ctypes.c_int),
+    "st_gate_wait": ([_vp], ctypes.c_int),
+    "st_stream_sync": ([_vp], ctypes.c_int),
+    "st_host_device_ptr": ([_vp, ctypes.POINTER(_vp)], ctypes.c_int),
+    "st_stream_wait": ([_vp, _vp], ctypes.c_int),
+    "st_gen_actions": ([_vp, _i64, _i64, _u64, _i64, _vp], ctypes.c_int),
+    "st_policy_greedy": ([_vp, _u64, _i64, ctypes.c_uint32, _vp, _vp], ctypes.c_int),
+    "st_debug_stamps": ([_vp, _vp, _i64], ctypes.c_int),
+    "st_last_error": ([], ctypes.c_char_p),
+    "st_abi_version": ([], ctypes.c_int),
+}
+EXPORTS = tuple(SIG)
+
+
 _lib = None
 
 
@@ -82,46 +119,6 @@ def load(path: str = LIB_PATH):
             f"libsimpletetris.so not found at {path}; build it with "
             "`make -C gym-simpletetris_amd/csrc` (the engine has no CPU fallback)")
     L = ctypes.CDLL(path)
-    vp, i32, i64, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
-    u32 = ctypes.c_uint32
-    sig = {
-        "st_create": ([ctypes.POINTER(vp), ctypes.POINTER(Config), ctypes.c_int, i64], ctypes.c_int),
-        "st_destroy": ([vp], ctypes.c_int),
-        "st_seed": ([vp, vp, vp], ctypes.c_int),
-        "st_reset": ([vp, vp, vp], ctypes.c_int),
-        "st_step": ([vp, vp, vp, vp, vp, vp], ctypes.c_int),
-        "st_step_f32": ([vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
-        "st_step_n": ([vp, vp, ctypes.c_int64, vp, vp, vp, vp, vp], ctypes.c_int),
-        "st_step_vec": ([vp, vp, vp, vp, vp, vp, vp, vp, vp], ctypes.c_int),
-        "st_rollout": ([vp, i32, vp, vp, vp, vp, vp, vp], ctypes.c_int),
-        "st_wire_words": ([i32, i32], ctypes.c_int),
-        "st_step_wire": ([vp, vp, vp, vp], ctypes.c_int),
-        "st_unwire": ([i32, i32, i64, vp, vp, vp, vp, vp], ctypes.c_int),
-        "st_unwire_shards": ([i32, i32, i64, i32, i64, vp, vp, vp, vp, vp], ctypes.c_int),
-        "st_obs_to_f32": ([vp, vp, vp, vp], ctypes.c_int),
-        "st_render": ([vp, vp, vp], ctypes.c_int),
-        "st_grayscale": ([vp, vp, i32, i32, i32, vp, vp], ctypes.c_int),
-        "st_state": ([vp, ctypes.POINTER(StateViews)], ctypes.c_int),
-        "st_copy": ([vp, vp, i64, vp], ctypes.c_int),
-        "st_mt_sync": ([vp, vp], ctypes.c_int),
-        "st_state_bytes": ([vp], i64),
-        "st_save": ([vp, vp, i64], ctypes.c_int),
-        "st_load": ([vp, vp, i64], ctypes.c_int),
-        "st_export_env": ([vp, i64, vp, vp, vp, u32, vp, vp], ctypes.c_int),
-        "st_export_words": ([i32, i32], ctypes.c_int),
-        "st_check_actions": ([vp, i64, vp, vp], ctypes.c_int),
-        "st_set_action_flag": ([vp, vp], ctypes.c_int),
-        "st_gate_actions": ([vp, vp, vp], ctypes.c_int),
-        "st_gate_wait": ([vp], ctypes.c_int),
-        "st_stream_sync": ([vp], ctypes.c_int),
-        "st_host_device_ptr": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
-        "st_stream_wait": ([vp, vp], ctypes.c_int),
-        "st_gen_actions": ([vp, i64, i64, u64, i64, vp], ctypes.c_int),
-        "st_policy_greedy": ([vp, u64, i64, ctypes.c_uint32, vp, vp], ctypes.c_int),
-        "st_debug_stamps": ([vp, vp, i64], ctypes.c_int),
-        "st_last_error": ([], ctypes.c_char_p),
-        "st_abi_version": ([], ctypes.c_int),
-    }
     # ST_AB_OLD_ABI=1: a diagnostic A/B of an older build -- tolerate the
     # entry points it predates (never the default, not even with ST_LIB set)
     ab_override = os.environ.get("ST_AB_OLD_ABI") == "1"
@@ -131,7 +128,7 @@ def load(path: str = LIB_PATH):
     if abi != ABI_VERSION and not ab_override:
         raise ImportError(f"{path}: libsimpletetris ABI {abi} != {ABI_VERSION} (rebuild it, or set "
                           "ST_AB_OLD_ABI=1 for a diagnostic A/B of an older build)")
-    for name, (args, res) in sig.items():
+    for name, (args, res) in SIG.items():
         if ab_override and not hasattr(L, name):
             continue
         fn = getattr(L, name)

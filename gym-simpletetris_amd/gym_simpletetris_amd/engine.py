@@ -49,6 +49,26 @@ def _mapped(t: torch.Tensor):
     return dp if rc == 0 and dp.value else None
 
 
+class _Pinned:
+    """A pinned host tensor (`host`) that a library call's result is read
+    back into.  The call writes at the device address `dst`: the host tensor
+    itself where the runtime maps it for the device, else (`staged`) a
+    device buffer of the same size, which land(stream) then copies to the
+    host tensor on the stream -- `if p.staged: p.land(s)` after the call (the
+    test is the call site's: a Python call per step shows in TetrisEnv.step)."""
+
+    def __init__(self, shape, dtype, device):
+        self.host = torch.empty(shape, dtype=dtype, pin_memory=True)
+        self.dst = _mapped(self.host)
+        self.staged = self.dst is None
+        if self.staged:
+            self._dev = torch.empty(shape, dtype=dtype, device=device)
+            self.dst = _ptr(self._dev)
+
+    def land(self, s) -> None:
+        C.check(C.load().st_copy(_ptr(self.host), self.dst, self.host.numel() * self.host.element_size(), s))
+
+
 def scalar_action(a) -> int:
     """value_action_map[a] (tetris_env.py:152-160, :245) for one action: ints,
     bools and numpy integers index by value; a float finds a key only when it
@@ -64,16 +84,53 @@ def scalar_action(a) -> int:
     return v
 
 
-def _bad_actions(x: torch.Tensor) -> torch.Tensor:
-    """Elementwise "not a key of value_action_map" for an action tensor (the
-    same rule as scalar_action: floats must be integral)."""
-    if x.dtype == torch.bool:
-        return torch.zeros_like(x)
-    if x.dtype.is_floating_point:
-        return ~((x >= 0) & (x <= 6) & (x == torch.floor(x)))
-    if x.dtype == torch.uint8:
+def _bad_actions(x):
+    """Elementwise "not a key of value_action_map" for an action array, a
+    numpy array or a torch tensor alike (the same rule as scalar_action:
+    floats must be integral).  A numpy array is judged in numpy: torch cannot
+    compare uint16 / uint32 / uint64."""
+    if isinstance(x, np.ndarray):
+        if x.dtype.kind not in "fiub":
+            raise TypeError(f"actions must be numbers, got {x.dtype}")
+        is_float, unsigned, floor = x.dtype.kind == "f", x.dtype.kind in "ub", np.floor
+    else:
+        is_float, unsigned, floor = x.dtype.is_floating_point, x.dtype in (torch.uint8, torch.bool), torch.floor
+    if is_float:
+        return ~((x >= 0) & (x <= 6) & (x == floor(x)))
+    if unsigned:
         return x > 6
     return (x < 0) | (x > 6)
+
+
+def _raise_bad_actions(x) -> None:
+    """The reference's KeyError (tetris_env.py:245) if `x` (numpy array or
+    torch tensor; on a device: one device->host sync) holds a bad action."""
+    bad = _bad_actions(x)
+    if bool(bad.any()):
+        raise KeyError(f"action {x[bad].reshape(-1)[0].item()} not in 0..6 (tetris_env.py:245)")
+
+
+def _check_tensor(t, name: str, shape, dtypes, device=None) -> None:
+    """ValueError unless `t` is a contiguous torch tensor of `shape` (None:
+    any extent) with one of `dtypes` on `device` (None: any GPU) -- the
+    kernels read and write it through its raw pointer."""
+    if not (isinstance(t, torch.Tensor) and t.dim() == len(shape) and t.dtype in dtypes and t.is_contiguous()
+            and all(w is None or w == g for w, g in zip(shape, t.shape))
+            and (t.device.type == "cuda" if device is None else t.device == device)):
+        got = (tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)
+        want = "[%s]" % ", ".join("*" if w is None else str(w) for w in shape)
+        raise ValueError(f"{name}: need a contiguous {'/'.join(map(str, dtypes))} {want} tensor "
+                         f"on {device or 'a GPU'}, got {got}")
+
+
+def _check_out(out, width: int, n: int, device):
+    """A caller's (packed obs int32 [width, n], reward int32 [n], done
+    bool/uint8 [n]) output tensors on `device`, checked (_check_tensor)."""
+    obs, reward, done = out
+    _check_tensor(obs, "out obs", (width, n), (torch.int32,), device)
+    _check_tensor(reward, "out reward", (n,), (torch.int32,), device)
+    _check_tensor(done, "out done", (n,), (torch.bool, torch.uint8), device)
+    return obs, reward, done
 
 
 def _from_dlpack(x):
@@ -196,102 +253,101 @@ class TetrisBatch:
             C.check(self._L.st_seed(self._ctx, ctypes.c_void_p(arr.ctypes.data), self._stream()))
         self._seeded = True
 
-    def _as_dev_u8(self, x, name) -> torch.Tensor:
+    def _intake(self, x, shape, name="actions"):
+        """`x` (torch tensor, DLPack producer, numpy array or anything numpy
+        takes) as a torch tensor -- a device array over the same memory, no
+        copy -- or a numpy array, of as many real numbers as `shape` holds."""
         x = _from_dlpack(x)
-        if isinstance(x, torch.Tensor):
-            t = x.to(device=self.device, dtype=torch.uint8)
+        if not isinstance(x, torch.Tensor):
+            x = np.asarray(x)
+        elif x.is_complex():
+            raise TypeError(f"{name} must be real numbers, got {x.dtype}")
+        if np.prod(x.shape) != np.prod(shape):
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(x.shape)}")
+        return x
+
+    def _to_dev_u8(self, x, shape, keep_bad: bool = False) -> torch.Tensor:
+        """_intake's array as a contiguous uint8 tensor of `shape` on the
+        engine's device (itself if it is one).  The cast wraps; `keep_bad`
+        keeps the bad actions of a tensor visible to a check on the device
+        as 255."""
+        if isinstance(x, np.ndarray):
+            return torch.as_tensor(x.astype(np.uint8).reshape(shape), device=self.device)
+        if x.dtype == torch.uint8 and x.device == self.device:
+            t = x
         else:
-            t = torch.as_tensor(np.asarray(x, dtype=np.uint8), device=self.device)
-        if t.numel() != self.n:
-            raise ValueError(f"{name} must have {self.n} entries, got {t.numel()}")
-        return t.contiguous()
+            t = x.to(device=self.device).to(torch.uint8)
+            if keep_bad:  # keep bad values visible to the kernel's check: a cast
+                # may wrap them into 0..6 (int16 256 -> 0, 2.5 -> 2); the sentinel is set after
+                # the cast, in uint8, so no source dtype has to hold 255 (int8 cannot)
+                t = t.masked_fill_(_bad_actions(x).to(self.device), 255)
+        return t.reshape(shape).contiguous()
+
+    def _action_check(self, on_dev: bool, can_gate: bool) -> str:
+        """Which check the reference's KeyError for an action outside
+        value_action_map (tetris_env.py:152-160, :245) comes from:
+          'host'   the input is not on the engine's device: checked where it
+                   lives, before anything is launched, whatever the mode;
+          'sync'   validate_actions=True at an entry point that cannot gate
+                   (rollouts, step_wire): on the device, one device->host sync;
+          'gate'   True at step() / the vector env's step: st_gate_actions
+                   (_gated_launch: the step is skipped entirely if an action
+                   was bad; the host waits for the check kernel only);
+          'kernel' 'async': the step kernel itself (st_set_action_flag: it sets
+                   a sticky word in mapped host memory when an action is > 6,
+                   polled by _raise_flagged without a sync);
+          'none'   False: no check (values > 6 act as idle)."""
+        if not on_dev:
+            return "host"
+        if self.validate_actions == "async":
+            return "kernel"
+        if self.validate_actions is True:
+            return "gate" if can_gate else "sync"
+        return "none"
 
     def _actions(self, x, lead=(), gate: bool = False):
-        """Actions as a contiguous uint8 device tensor of shape lead + (n,).
-        The reference raises KeyError for an action outside value_action_map
-        (tetris_env.py:152-160, :245); a uint8 cast would wrap -1 to 255 and
-        263 to 7, so values are checked BEFORE it:
-          validate_actions=True: immediately.  Host arrays on the host; a
-            device tensor, with `gate` (step() / the vector env's step): by
-            st_gate_actions -- returned as (tensor, True), and the caller
-            gates its step launch on it and calls _gate_wait() after it (the
-            step is skipped entirely if an action was bad; the host waits for
-            the check kernel only, not the stream); without `gate`
-            (rollouts, step_wire) one device->host sync;
-          'async': by the step kernel itself (st_set_action_flag: the kernel
-            sets a sticky word in mapped host memory when an action is > 6,
-            polled here without a sync); non-uint8 tensors get their bad values
-            mapped to 255 on the device first, so the kernel sees them;
-          False: no check (values > 6 act as idle)."""
+        """(actions as a contiguous uint8 device tensor of shape lead + (n,),
+        gated).  A uint8 cast would wrap -1 to 255 and 263 to 7, so the values
+        are checked BEFORE it, by the check _action_check names; `gate` says
+        that the caller can gate its launch, and `gated` that it has to
+        (_gated_launch).  The checks on the device ('gate', 'kernel') see
+        uint8: bad values of other dtypes reach them as 255."""
         shape = tuple(lead) + (self.n,)
-        asyn = self.validate_actions == "async"
-        gated = gate and self.validate_actions is True
-        if asyn:
+        mode = self.validate_actions
+        if mode == "async":
             self._raise_flagged()
         if (type(x) is torch.Tensor and x.dtype == torch.uint8 and x.device == self.device
                 and x.is_contiguous() and tuple(x.shape) == shape):
-            # an RL loop's own device buffer: checked in the step kernel
-            # ('async'), by the gate (True), or not at all
-            if gated:
+            # an RL loop's own device buffer, as it is: checked in the step
+            # kernel ('async'), by the gate (True), or not at all
+            if mode is not True:
+                return x, False
+            if gate:
                 return x, True
-            if self.validate_actions is not True:
-                return (x, False) if gate else x
-        x = _from_dlpack(x)
-        if isinstance(x, torch.Tensor):
-            if x.is_complex():
-                raise TypeError(f"actions must be real numbers, got {x.dtype}")
-            if tuple(x.shape) != shape and x.numel() != int(np.prod(shape)):
-                raise ValueError(f"actions must have shape {shape}, got {tuple(x.shape)}")
-            on_dev = x.device == self.device
-            if (self.validate_actions is True and not (gated and on_dev)) or not on_dev:
-                bad = _bad_actions(x)
-                if bool(bad.any()):
-                    v = x[bad].flatten()[0].item()
-                    raise KeyError(f"action {v} not in 0..6 (tetris_env.py:245)")
-            if x.dtype == torch.uint8 and on_dev:
-                t = x
-            else:
-                t = x.to(device=self.device).to(torch.uint8)
-                if asyn or (gated and on_dev):  # keep bad values visible to the kernel's check: a cast
-                    # may wrap them into 0..6 (int16 256 -> 0, 2.5 -> 2); the sentinel is set after
-                    # the cast, in uint8, so no source dtype has to hold 255 (int8 cannot)
-                    t = t.masked_fill_(_bad_actions(x).to(self.device), 255)
-            t = t.reshape(shape).contiguous()
-            return (t, gated and on_dev) if gate else t
-        a = np.asarray(x)
-        if a.size != int(np.prod(shape)):
-            raise ValueError(f"actions must have shape {shape}, got {a.shape}")
-        if a.dtype.kind == "f":
-            ok = (a >= 0) & (a <= 6) & (a == np.floor(a))
-        elif a.dtype.kind in "iub":
-            ok = (a >= 0) & (a <= 6)
-        else:
-            raise TypeError(f"actions must be numbers, got {a.dtype}")
-        if a.size and not ok.all():
-            v = a.flat[np.flatnonzero(~ok)[0]]
-            raise KeyError(f"action {v} not in 0..6 (tetris_env.py:245)")
-        t = torch.as_tensor(a.astype(np.uint8).reshape(shape), device=self.device)
-        return (t, False) if gate else t
+        x = self._intake(x, shape)
+        check = self._action_check(isinstance(x, torch.Tensor) and x.device == self.device, gate)
+        if check in ("host", "sync"):
+            _raise_bad_actions(x)
+        return self._to_dev_u8(x, shape, keep_bad=check in ("gate", "kernel")), check == "gate"
 
-    def _gate_launch(self, a: torch.Tensor, s) -> None:
-        """st_gate_actions: check `a` on stream s; the next step launch on
-        this context is skipped if an action is outside 0..6."""
+    def _gated_launch(self, a: torch.Tensor, s, fn, args) -> None:
+        """The step launch fn(*args) on stream s behind st_gate_actions' check
+        of `a` (for a step _actions returned as gated): that launch skips
+        every env if an action is outside 0..6; then st_gate_wait -- the host
+        waits for the check, not for the step behind it -- and the
+        reference's KeyError (tetris_env.py:245): the step changed nothing.
+        An ungated step is C.check(fn(*args)) at the call site: a Python call
+        more per step shows in the vector env's step time."""
         C.check(self._L.st_gate_actions(self._ctx, _ptr(a), s))
-
-    def _gate_wait(self) -> None:
-        """st_gate_wait: wait for the gate's check (not the step behind it)
-        and raise the reference's KeyError (tetris_env.py:245) if it saw an
-        action outside 0..6 -- the gated step changed nothing."""
-        rc = self._L.st_gate_wait(self._ctx)
+        try:
+            C.check(fn(*args))
+        finally:  # st_gate_wait ends the gate, also when the launch raised (its answer is
+            # moot then): it cannot gate a later step
+            rc = self._L.st_gate_wait(self._ctx)
         if rc < 0:
             C.check(rc)
         if rc:
             raise KeyError("an action outside 0..6 (tetris_env.py:245); no env was stepped")
-
-    def _gate_abort(self) -> None:
-        """The gated step's launch failed: end the gate (st_gate_wait also
-        disarms it) so that it cannot gate a later step; its answer is moot."""
-        self._L.st_gate_wait(self._ctx)
 
     def _raise_flagged(self):
         if self._flag_np[0]:
@@ -311,7 +367,7 @@ class TetrisBatch:
         """TetrisEngine.clear() on every env (mask None) or where mask != 0."""
         if not self._seeded:
             raise RuntimeError("seed() before reset()")
-        m = None if mask is None else self._as_dev_u8(mask, "mask")
+        m = None if mask is None else self._to_dev_u8(self._intake(mask, (self.n,), "mask"), (self.n,))
         with torch.cuda.device(self.device):
             C.check(self._L.st_reset(self._ctx, _ptr(m), self._stream()))
 
@@ -324,38 +380,37 @@ class TetrisBatch:
         if obs not in ("packed", "f32", "none"):
             raise ValueError("obs must be 'packed', 'f32' or 'none'")
         a, gated = self._actions(actions, gate=True)
-        o_t, r_t, d_t = (self.obs, self.reward, self.done) if out is None else out
-        if out is not None:
-            for t, dt, shape in ((o_t, torch.int32, (self.width, self.n)),
-                                 (r_t, torch.int32, (self.n,)), (d_t, None, (self.n,))):
-                if t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous() \
-                        or (dt is not None and t.dtype != dt) \
-                        or (dt is None and t.dtype not in (torch.uint8, torch.bool)):
-                    raise ValueError(f"out tensor {tuple(t.shape)} {t.dtype} on {t.device}: "
-                                     f"need contiguous {shape} on {self.device}")
+        o_t, r_t, d_t = (self.obs, self.reward, self.done) if out is None \
+            else _check_out(out, self.width, self.n, self.device)
         s = self._stream()
-        if gated:  # validate_actions=True, device actions: the gated step (st_gate_actions)
-            self._gate_launch(a, s)
-        try:
-            # no torch.cuda.device() context: st_step selects the context's device itself
-            if obs == "f32":
-                if self.obs_f32 is None:
-                    self.obs_f32 = torch.zeros((self.n, self.width, self.height),
-                                               dtype=torch.float32, device=self.device)
-                C.check(self._L.st_step_f32(self._ctx, _ptr(a), _ptr(o_t), _ptr(self.obs_f32),
-                                            _ptr(r_t), _ptr(d_t), s))
-            else:
-                C.check(self._L.st_step(self._ctx, _ptr(a), _ptr(o_t) if obs == "packed" else None,
-                                        _ptr(r_t), _ptr(d_t), s))
-        except BaseException:
-            if gated:
-                self._gate_abort()
-            raise
-        if gated:
-            self._gate_wait()
+        # no torch.cuda.device() context: st_step selects the context's device itself
         if obs == "f32":
-            return self.obs_f32, r_t, d_t
-        return (o_t if obs == "packed" else None), r_t, d_t
+            o_ret = self._f32_buffer()
+            fn, args = self._L.st_step_f32, (self._ctx, _ptr(a), _ptr(o_t), _ptr(o_ret), _ptr(r_t), _ptr(d_t), s)
+        else:
+            o_ret = o_t if obs == "packed" else None
+            fn, args = self._L.st_step, (self._ctx, _ptr(a), _ptr(o_ret), _ptr(r_t), _ptr(d_t), s)
+        if gated:  # validate_actions=True, device actions
+            self._gated_launch(a, s, fn, args)
+        else:
+            C.check(fn(*args))
+        return o_ret, r_t, d_t
+
+    def _f32_buffer(self) -> torch.Tensor:
+        """The float32 obs [n][W][H] that step() and step_n() reuse (made on first use)."""
+        if self.obs_f32 is None:
+            self.obs_f32 = torch.zeros((self.n, self.width, self.height), dtype=torch.float32, device=self.device)
+        return self.obs_f32
+
+    def _k_actions(self, actions):
+        """rollout() / step_n(): a [K, n] integer tensor (or DLPack producer),
+        K >= 1, through _actions -> (uint8 device tensor [K, n], K)."""
+        actions = _from_dlpack(actions)
+        if not isinstance(actions, torch.Tensor) or actions.dim() != 2 or actions.shape[1] != self.n \
+                or actions.shape[0] < 1:
+            raise ValueError(f"actions must be a [K, {self.n}] integer tensor")
+        K = int(actions.shape[0])
+        return self._actions(actions, lead=(K,))[0], K
 
     @property
     def wire_words(self) -> int:
@@ -367,14 +422,12 @@ class TetrisBatch:
         of obs / reward / done: int32 [wire_words, n], per env column x's obs
         bits at bit x*H, then the reward's 32 bits and done
         (st_step_wire; `unwire` restores step()'s outputs bit-exactly)."""
-        a = self._actions(actions)
+        a, _ = self._actions(actions)
         shape = (self.wire_words, self.n)
         if out is None:
             out = torch.empty(shape, dtype=torch.int32, device=self.device)
-        elif out.device != self.device or tuple(out.shape) != shape or out.dtype != torch.int32 \
-                or not out.is_contiguous():
-            raise ValueError(f"out tensor {tuple(out.shape)} {out.dtype} on {out.device}: "
-                             f"need contiguous int32 {shape} on {self.device}")
+        else:
+            _check_tensor(out, "out", shape, (torch.int32,), self.device)
         C.check(self._L.st_step_wire(self._ctx, _ptr(a), _ptr(out), self._stream()))
         return out
 
@@ -386,12 +439,7 @@ class TetrisBatch:
         [K, n, W, H] ('f32') or None ('none'); reward int32 [K, n]; done bool
         [K, n].  Identical to K calls of step().  `out` may supply the output
         tensors (keys 'obs', 'obs_f32', 'reward', 'done') to reuse buffers."""
-        actions = _from_dlpack(actions)
-        if not isinstance(actions, torch.Tensor) or actions.dim() != 2 or actions.shape[1] != self.n \
-                or actions.shape[0] < 1:
-            raise ValueError(f"actions must be a [K, {self.n}] integer tensor")
-        K = int(actions.shape[0])
-        actions = self._actions(actions, lead=(K,))
+        actions, K = self._k_actions(actions)
         out = {} if out is None else out
         W, H, n, dev = self.width, self.height, self.n, self.device
 
@@ -417,25 +465,18 @@ class TetrisBatch:
         (checked like rollout()'s).  Identical to K calls of step(); returns
         the LAST step's (obs, reward, done) in the engine's reused buffers
         ('packed': int32 [W, n], 'f32': float32 [n, W, H], 'none': None)."""
-        actions = _from_dlpack(actions)
-        if not isinstance(actions, torch.Tensor) or actions.dim() != 2 or actions.shape[1] != self.n \
-                or actions.shape[0] < 1:
-            raise ValueError(f"actions must be a [K, {self.n}] integer tensor")
         if obs not in ("packed", "f32", "none"):
             raise ValueError("obs: 'packed', 'f32' or 'none'")
-        K = int(actions.shape[0])
-        actions = self._actions(actions, lead=(K,))
-        if obs == "f32" and self.obs_f32 is None:
-            self.obs_f32 = torch.zeros((self.n, self.width, self.height), dtype=torch.float32, device=self.device)
+        actions, K = self._k_actions(actions)
+        f = self._f32_buffer() if obs == "f32" else None
         row = actions.stride(0)
         base = actions.data_ptr()
         ptrs = (ctypes.c_void_p * K)(*[base + t * row for t in range(K)])
         C.check(self._L.st_step_n(self._ctx, ctypes.addressof(ptrs), K,
-                                  _ptr(self.obs) if obs != "none" else None,
-                                  _ptr(self.obs_f32) if obs == "f32" else None,
+                                  _ptr(self.obs) if obs != "none" else None, _ptr(f),
                                   _ptr(self.reward), _ptr(self.done), self._stream()))
         if obs == "f32":
-            return self.obs_f32, self.reward, self.done
+            return f, self.reward, self.done
         return (self.obs if obs == "packed" else None), self.reward, self.done
 
     # ------------------------------------------------------------ observations
@@ -465,6 +506,14 @@ class TetrisBatch:
 
     def _view_ptr(self, name):
         return getattr(self._views, name)
+
+    def _stat_ptr(self, row: int, env: int = 0) -> ctypes.c_void_p:
+        """Device address of counter row `row` (C.STAT) of one env: the
+        counters are int32 [NSTAT][stride]."""
+        return ctypes.c_void_p(self._views.stats + (row * self.stride + env) * 4)
+
+    def _pinned(self, shape, dtype) -> "_Pinned":
+        return _Pinned(shape, dtype, self.device)
 
     def sync_mt(self):
         """Complete the generations the lazy in-kernel MT twist left in
@@ -595,9 +644,7 @@ def unwire(wire: torch.Tensor, width: int, height: int):
     step()'s outputs.  Runs on the tensor's device, on torch's current stream."""
     L = C.load()
     words = C.check_count(L.st_wire_words(width, height))
-    if not isinstance(wire, torch.Tensor) or wire.device.type != "cuda" or wire.dtype != torch.int32 \
-            or wire.dim() != 2 or wire.shape[0] != words or not wire.is_contiguous():
-        raise ValueError(f"wire must be a contiguous int32 [{words}, n] GPU tensor")
+    _check_tensor(wire, "wire", (words, None), (torch.int32,))
     n = wire.shape[1]
     obs = torch.empty((width, n), dtype=torch.int32, device=wire.device)
     reward = torch.empty(n, dtype=torch.int32, device=wire.device)
@@ -618,27 +665,14 @@ def unwire_shards(recv: torch.Tensor, width: int, height: int, n_global: int, ou
     Runs on the tensor's device, on torch's current stream."""
     L = C.load()
     words = C.check_count(L.st_wire_words(width, height))
-    if not isinstance(recv, torch.Tensor) or recv.device.type != "cuda" or recv.dtype != torch.int32 \
-            or recv.dim() != 3 or recv.shape[1] != words or not recv.is_contiguous():
-        raise ValueError(f"recv must be a contiguous int32 [shards, {words}, n_cap] GPU tensor")
+    _check_tensor(recv, "recv", (None, words, None), (torch.int32,))  # [shards, words, n_cap]
     shards, _, cap = recv.shape
     if out is None:
-        out = (torch.empty((width, n_global), dtype=torch.int32, device=recv.device),
-               torch.empty(n_global, dtype=torch.int32, device=recv.device),
-               torch.empty(n_global, dtype=torch.bool, device=recv.device))
-    else:  # the kernel writes through raw pointers: check every output like recv
-        out = tuple(out)
-        want = (((width, n_global), (torch.int32,)), ((n_global,), (torch.int32,)),
-                ((n_global,), (torch.bool, torch.uint8)))
-        if len(out) != 3:
-            raise ValueError("out must be (obs, reward, done)")
-        for name, t, (shape, dts) in zip(("obs", "reward", "done"), out, want):
-            if not isinstance(t, torch.Tensor) or t.device != recv.device or tuple(t.shape) != shape \
-                    or t.dtype not in dts or not t.is_contiguous():
-                got = (tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)
-                raise ValueError(f"out {name}: need a contiguous {'/'.join(map(str, dts))} {shape} tensor "
-                                 f"on {recv.device}, got {got}")
-    obs, reward, done = out
+        obs, reward, done = (torch.empty((width, n_global), dtype=torch.int32, device=recv.device),
+                             torch.empty(n_global, dtype=torch.int32, device=recv.device),
+                             torch.empty(n_global, dtype=torch.bool, device=recv.device))
+    else:  # the kernel writes through raw pointers: every output is checked like recv
+        obs, reward, done = _check_out(out, width, n_global, recv.device)
     with torch.cuda.device(recv.device):
         C.check(L.st_unwire_shards(width, height, n_global, shards, cap, _ptr(recv), _ptr(obs), _ptr(reward),
                                    _ptr(done), _stream_ptr(recv.device)))

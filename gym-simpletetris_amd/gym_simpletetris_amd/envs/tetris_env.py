@@ -30,7 +30,7 @@ import torch
 
 from .. import _lib as C
 from .. import spaces
-from ..engine import SHAPE_NAMES, TetrisBatch, _mapped, scalar_action
+from ..engine import SHAPE_NAMES, TetrisBatch, scalar_action
 
 
 # counter rows of the export record (st_stat)
@@ -118,20 +118,16 @@ class TetrisEnv:
         self._nrec = int(L.st_export_words(width, height))
         self._parts = (C.EXPORT_MT if rng == "global" else 0) | (C.EXPORT_OBS_F32 if obs_type == "ram" else 0)
         self._f32_at = width + 2 + C.NSTAT + C.MT_N  # the record's float32 obs
-        self._d_rec = torch.empty(self._nrec, dtype=torch.int32, device=dev)
-        self._h_rec = torch.empty(self._nrec, dtype=torch.int32, pin_memory=True)
-        self._h_rec_np = self._h_rec.numpy()
-        self._zeros = torch.zeros((width, 1), dtype=torch.int32, device=dev)
-        self._ch = 1 if obs_type == "grayscale" else 3
-        if obs_type in ("grayscale", "rgb"):
-            self._d_img = torch.empty((1, 84, 84, self._ch), dtype=torch.float32, device=dev)
-            self._h_img = torch.empty((1, 84, 84, self._ch), dtype=torch.float32, pin_memory=True)
-        self._h_mt = np.zeros(C.MT_N, np.uint32)
-        self._h_idx = np.zeros(1, np.int32)
         # the export and image kernels write straight into the pinned buffers
         # when the runtime maps them for the device (else: device buffer + copy)
-        self._rec_dst = _mapped(self._h_rec)
-        self._img_dst = _mapped(self._h_img) if obs_type in ("grayscale", "rgb") else None
+        self._rec = self.engine._pinned(self._nrec, torch.int32)
+        self._h_rec_np = self._rec.host.numpy()
+        self._zeros = torch.zeros((width, 1), dtype=torch.int32, device=dev)
+        self._ch = 1 if obs_type == "grayscale" else 3
+        self._img = self.engine._pinned((1, 84, 84, self._ch), torch.float32) \
+            if obs_type in ("grayscale", "rgb") else None
+        self._h_mt = np.zeros(C.MT_N, np.uint32)
+        self._h_idx = np.zeros(1, np.int32)
         # per-step constants: output pointers, the stream current at
         # construction (the env issues all its work there), a direct
         # hipStreamSynchronize (torch's costs ~3 us more per call)
@@ -163,13 +159,12 @@ class TetrisEnv:
         internal = state[1]
         self._h_mt[:] = np.asarray(internal[:C.MT_N], dtype=np.uint32)
         self._h_idx[0] = internal[C.MT_N]
-        v = self.engine._views
-        L = self.engine._L
+        eng = self.engine
+        L = eng._L
         s = self._stream()
-        C.check(L.st_copy(ctypes.c_void_p(v.mt), ctypes.c_void_p(self._h_mt.ctypes.data),
+        C.check(L.st_copy(ctypes.c_void_p(eng._view_ptr("mt")), ctypes.c_void_p(self._h_mt.ctypes.data),
                           C.MT_N * 4, s))
-        C.check(L.st_copy(ctypes.c_void_p(v.stats + C.STAT["mt_index"] * v.stride * 4),
-                          ctypes.c_void_p(self._h_idx.ctypes.data), 4, s))
+        C.check(L.st_copy(eng._stat_ptr(C.STAT["mt_index"]), ctypes.c_void_p(self._h_idx.ctypes.data), 4, s))
         self._rng_sync_state = state  # the device now mirrors CPython's state
 
     def _readback(self, obs_ptr, rew_ptr, done_ptr, prev_idx=None):
@@ -183,22 +178,15 @@ class TetrisEnv:
         eng = self.engine
         L, ctx = eng._L, eng._ctx
         s = self._stream()
-        if self._rec_dst is not None:
-            C.check(L.st_export_env(ctx, 0, obs_ptr, rew_ptr, done_ptr, self._parts, self._rec_dst, s))
-        else:
-            C.check(L.st_export_env(ctx, 0, obs_ptr, rew_ptr, done_ptr, self._parts,
-                                    ctypes.c_void_p(self._d_rec.data_ptr()), s))
-            C.check(L.st_copy(ctypes.c_void_p(self._h_rec.data_ptr()), ctypes.c_void_p(self._d_rec.data_ptr()),
-                              self._nrec * 4, s))
-        img = None
-        if self.obs_type in ("grayscale", "rgb"):
-            src = obs_ptr if obs_ptr is not None else ctypes.c_void_p(self._zeros.data_ptr())
-            if self._img_dst is not None:
-                C.check(L.st_grayscale(ctx, src, 84, self._ch, 0, self._img_dst, s))
-            else:
-                C.check(L.st_grayscale(ctx, src, 84, self._ch, 0, ctypes.c_void_p(self._d_img.data_ptr()), s))
-                C.check(L.st_copy(ctypes.c_void_p(self._h_img.data_ptr()), ctypes.c_void_p(self._d_img.data_ptr()),
-                                  self._d_img.numel() * 4, s))
+        rec, img = self._rec, self._img
+        C.check(L.st_export_env(ctx, 0, obs_ptr, rew_ptr, done_ptr, self._parts, rec.dst, s))
+        if rec.staged:
+            rec.land(s)
+        if img is not None:
+            src = obs_ptr if obs_ptr is not None else self._pz
+            C.check(L.st_grayscale(ctx, src, 84, self._ch, 0, img.dst, s))
+            if img.staged:
+                img.land(s)
         self._sync()
         rec = self._h_rec_np
         W = self.width
@@ -217,8 +205,8 @@ class TetrisEnv:
                 new = (old[0], tuple(mt.tolist()) + (idx,), old[2])
                 random.setstate(new)
                 self._rng_sync_state = new
-        if img is None and self.obs_type in ("grayscale", "rgb"):
-            img = self._h_img.numpy()[0].copy()
+        if img is not None:
+            img = img.host.numpy()[0].copy()
         return obs, int(rec[W]), bool(rec[W + 1]), st, img
 
     # ------------------------------------------------------------- gym API
@@ -262,12 +250,11 @@ class TetrisEnv:
             raise ValueError("info['statistics'] may only hold int32 counts for the keys "
                              f"{SHAPE_NAMES} (got {dict(d)!r})")
         eng = self.engine
-        L, s, v = eng._L, self._stream(), eng._views
+        L, s = eng._L, self._stream()
         C.check(L.st_mt_sync(eng._ctx, s))
         cnt = np.asarray(vals, dtype=np.int32)
         for i in range(7):
-            C.check(L.st_copy(ctypes.c_void_p(v.stats + (C.STAT["count0"] + i) * v.stride * 4),
-                              ctypes.c_void_p(cnt.ctypes.data + 4 * i), 4, s))
+            C.check(L.st_copy(eng._stat_ptr(_C0 + i), ctypes.c_void_p(cnt.ctypes.data + 4 * i), 4, s))
         self._sync()  # (cnt is pageable host memory)
         self._shape_vals = vals
         if self._stats is not None:
@@ -704,6 +691,7 @@ class TetrisVecEnv:
         eng = self.engine
         a, gated = eng._actions(actions, gate=True)
         s = eng._stream()
+        # the slot this step writes (chosen inline: a helper call per step shows in the step time)
         k0 = self._k
         if self.copy:  # this step's outputs, the caller's from now on
             slot, reused = self._pool.take(self._new_slot)
@@ -722,17 +710,12 @@ class TetrisVecEnv:
         prev = slot.stream
         slot.stream = s.value
         po, pf, pr, pd, pfin, pinfo = slot.ptrs
+        args = (eng._ctx, ctypes.c_void_p(a.data_ptr()), po, pf, pr, pd, pfin, pinfo, s)
         try:
-            if gated:  # validate_actions=True, device actions: the step is gated (st_gate_actions)
-                eng._gate_launch(a, s)
-            try:
-                C.check(self._step_vec(eng._ctx, ctypes.c_void_p(a.data_ptr()), po, pf, pr, pd, pfin, pinfo, s))
-            except BaseException:
-                if gated:
-                    eng._gate_abort()
-                raise
-            if gated:
-                eng._gate_wait()  # waits for the check only; raises KeyError if the step was skipped
+            if gated:  # validate_actions=True, device actions: KeyError if the step was skipped
+                eng._gated_launch(a, s, self._step_vec, args)
+            else:
+                C.check(self._step_vec(*args))
         except BaseException:
             # a step that raised wrote nothing: copy=False's alternation stays
             # where it was, so the next step takes this slot again and the last

@@ -5,6 +5,7 @@ to run without a GPU (no CPU fallback)."""
 import ctypes
 import os
 import re
+import warnings
 
 import numpy as np
 import pytest
@@ -112,6 +113,50 @@ def test_scalar_action_follows_the_reference_dict():
             scalar_action(a)
         with pytest.raises((KeyError, TypeError)):
             ref[a]
+
+
+ACTION_VALUES = (-1, 0, 3, 6, 7, 255, 256, 263, -0.0, 2.0, 2.5, 6.0, 6.5, float("nan"), float("inf"), True, False)
+ACTION_DTYPES = ("int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64",
+                 "float16", "float32", "float64", "bool")
+# torch (2.10) has no comparison kernels for these: `x < 0` raises
+# NotImplementedError, so their torch cells are the only ones left out (and
+# the reason numpy input is checked in numpy, not routed through torch)
+TORCH_CANNOT_COMPARE = ("uint16", "uint32", "uint64")
+
+
+def test_action_rule_is_one_rule_for_scalars_numpy_and_torch():
+    """"Not a key of value_action_map" (tetris_env.py:152-160, :245) as a
+    table, values x dtypes: each value cast to each dtype (so -1 as uint8 is
+    255, 2.5 as int32 is 2, nan as bool is True) is accepted or refused alike
+    by scalar_action, by the array rule on a numpy array and by the array rule
+    on the same data as a CPU torch tensor -- and as the reference's dict
+    does.  The array rule is reached the way every caller reaches it, through
+    TetrisBatch._actions (validate_actions=True), on a bare instance whose
+    device is the CPU: no GPU call is made."""
+    from gym_simpletetris_amd.engine import TetrisBatch, scalar_action
+    ref = {i: i for i in range(7)}
+    eng = object.__new__(TetrisBatch)
+    eng.n, eng.device, eng.validate_actions = 1, torch.device("cpu"), True
+
+    def refused(fn, x):
+        try:
+            fn(x)
+        except KeyError:
+            return True
+        return False
+    cells = 0
+    for value in ACTION_VALUES:
+        for dt in ACTION_DTYPES:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")  # nan / inf / 263 -> an integer dtype: "invalid value"
+                a = np.array([value]).astype(dt)
+            want = refused(ref.__getitem__, a[0].item())
+            got = {"scalar": refused(scalar_action, a[0]), "numpy": refused(eng._actions, a)}
+            if dt not in TORCH_CANNOT_COMPARE:
+                got["torch"] = refused(eng._actions, torch.from_numpy(a))
+            assert all(g == want for g in got.values()), (value, dt, a[0], want, got)
+            cells += len(got)
+    assert cells == len(ACTION_VALUES) * (3 * len(ACTION_DTYPES) - len(TORCH_CANNOT_COMPARE))
 
 
 def test_import_leaves_hip_environment_alone():

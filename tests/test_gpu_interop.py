@@ -30,7 +30,7 @@ def test_dlpack_actions_zero_copy_and_equal():
     acts = torch.empty((T, n), dtype=torch.uint8, device=a.device)
     for t in range(T):
         a.gen_actions(t, 0x99, out=acts[t])
-    assert b._actions(Foreign(acts[0])).data_ptr() == acts[0].data_ptr()  # no copy
+    assert b._actions(Foreign(acts[0]))[0].data_ptr() == acts[0].data_ptr()  # no copy
     for t in range(T // 2):
         oa, ra, da = a.step(acts[t])
         ob, rb, db = b.step(Foreign(acts[t]))

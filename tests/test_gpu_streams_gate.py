@@ -84,7 +84,7 @@ def test_gate_ends_at_wait_even_without_its_step():
     pointer: ST_EINVAL before anything is queued) ends at st_gate_wait -- the
     next, ungated st_step is an ordinary step, not skipped by the stale
     answer (TetrisBatch.step and TetrisVecEnv.step end a gate the same way,
-    _gate_abort, when their step launch raises)."""
+    in _gated_launch, when their step launch raises)."""
     import ctypes
     G = _engine()
     from gym_simpletetris_amd import _lib as C

@@ -20,8 +20,10 @@ def t(label, fn):
     print(f"{label:34s} host {(t1-t0)/N*1e6:7.2f} us  wall {(t2-t0)/N*1e6:7.2f} us", flush=True)
 t("vec.step", lambda: v.step(a))
 t("engine.step packed", lambda: v.engine.step(a, obs="packed"))
-t("VecInfo()", lambda: VecInfo(v.engine))
-t("engine._actions", lambda: v.engine._actions(a))
+slot = v._new_slot()
+t("VecInfo()", lambda: VecInfo(v, slot))
+t("engine._actions -> (a, gated)", lambda: v.engine._actions(a, gate=True))
+t("pool.take", lambda: v._pool.take(v._new_slot))
 t("current_stream ptr", lambda: ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
 def ctx():
     with torch.cuda.device(dev):
