@@ -21,6 +21,7 @@ Fixtures:
   grayscale.npz        F5  convert_grayscale images (next row, R19)
   render.npz           F5b engine.render(), render("rgb_array") and grayscale/rgb obs
                            along uniform-action games (python gen_golden.py render)
+(python gen_golden.py crafted writes crafted.npz alone.)
 
 Usage: python tests/golden/gen_golden.py  (writes next to this file)
 """
@@ -353,6 +354,51 @@ def crafted_cases():
     # 12. right edge, I horizontal near the wall.
     cases.append(dict(name="right_edge", cfg={}, seed=37, board=np.zeros((W, H)), shape=5,
                       rot=3, ax=6, ay=5, counters={}, actions=[1, 1, 1, 0, 5, 1, 1, 1, 2]))
+    # 13. a vertical I hard-dropped into a one-column well whose window reaches
+    #     row 0 (or above it): the lock survives only if it clears a row.
+    def row(*empty, w=W):
+        return "".join("." if x in empty else "#" for x in range(w))
+
+    c = 4
+    support = {y: row((3 * y) % 4) for y in range(4, H)}  # non-full rows, the gap never at c
+    top1 = {**support, **{0: row(c, 8), 1: row(c, 0), 2: row(c), 3: row(c, 6)}}
+    cases.append(dict(name="top_lock_clear1", cfg={}, seed=41, board=board_from_rows(W, H, top1),
+                      shape=5, rot=0, ax=c, ay=0, counters={}, actions=[2, 6, 2]))
+    top3 = {**support, **{0: row(c), 1: row(c, 9), 2: row(c), 3: row(c)}}
+    cases.append(dict(name="top_lock_clear_split",
+                      cfg=dict(high_scoring=True, penalise_height=True, penalise_holes=True), seed=43,
+                      board=board_from_rows(W, H, top3), shape=5, rot=0, ax=c, ay=0,
+                      counters=dict(holes=16), actions=[2, 6, 6]))
+    top0 = {**support, **{0: row(c, 8), 1: row(c, 0), 2: row(c, 2), 3: row(c, 6)}}
+    cases.append(dict(name="top_lock_death", cfg={}, seed=47, board=board_from_rows(W, H, top0),
+                      shape=5, rot=0, ax=c, ay=0, counters={}, actions=[2, 6, 2]))
+    # the well 3 deep: the I's top cell lies above the board (never painted)
+    clip = {**support, **{0: row(c, 1), 1: row(c), 2: row(c), 3: row(5)}}
+    cases.append(dict(name="clipped_lock_clear",
+                      cfg=dict(penalise_holes_increase=True, penalise_height_increase=True), seed=53,
+                      board=board_from_rows(W, H, clip), shape=5, rot=0, ax=c, ay=0,
+                      counters=dict(holes=23, piece_height=17), actions=[2, 6, 6]))
+    # 14. rows that are full before the lock (a host-written board): 6 of them
+    #     and the 2 the piece completes clear together.  (Not with
+    #     advanced_clears: the reference indexes a 5-entry list there.)
+    pre = {y: row() for y in range(14, H)}
+    pre.update({10: row(c, 1), 11: row(c, 9), 12: row(c), 13: row(c), 9: "##......#.", 8: ".#........"})
+    for name, cfg in [("prefull_default", {}),
+                      ("prefull_high", dict(high_scoring=True, penalise_holes=True))]:
+        cases.append(dict(name=name, cfg=cfg, seed=59, board=board_from_rows(W, H, pre), shape=5,
+                          rot=0, ax=c, ay=0, counters=dict(holes=3), actions=[2, 6, 6]))
+    # 15. a 4-row clear on a board taller than 25 rows, debris above it.
+    tall = {y: row(2, w=5) for y in range(23, 27)}
+    tall.update({22: "#...#", 21: "##...", 20: "...##", 19: "#....", 17: "....#"})
+    cases.append(dict(name="tall_tetris",
+                      cfg=dict(width=5, height=27, advanced_clears=True, penalise_holes_increase=True),
+                      seed=61, board=board_from_rows(5, 27, tall), shape=5, rot=0, ax=2, ay=0,
+                      counters=dict(holes=2), actions=[2, 6, 6]))
+    # 16. a split clear on a small board: rows {5, 7, 8} around a non-full row 6.
+    small = {5: row(3, w=6), 6: row(3, 0, w=6), 7: row(3, w=6), 8: row(3, w=6), 4: "#....#", 3: ".....#"}
+    cases.append(dict(name="small_split", cfg=dict(width=6, height=9, penalise_height_increase=True),
+                      seed=67, board=board_from_rows(6, 9, small), shape=5, rot=0, ax=3, ay=0,
+                      counters=dict(piece_height=2), actions=[2, 6, 6]))
     return cases
 
 
@@ -487,7 +533,11 @@ def main(which=GENERATORS):
     ref = load_reference()
     if "render" in which:
         gen_render()
-    if not set(which) - {"render"}:
+    rest = set(which) - {"render"}
+    if not rest:
+        return
+    if rest == {"crafted"}:
+        gen_crafted()
         return
     gen_mt()
     gen_crafted()
@@ -499,6 +549,6 @@ def main(which=GENERATORS):
 
 
 if __name__ == "__main__":
-    # no arguments: every fixture; else a subset of GENERATORS (only "render"
-    # is generated on its own, the others are written together)
+    # no arguments: every fixture; else a subset of GENERATORS ("render" and
+    # "crafted" are generated on their own, the others are written together)
     main(tuple(sys.argv[1:]) or GENERATORS)
