@@ -191,6 +191,42 @@ class OracleBatch:
         for k, v in counters.items():
             setattr(e, k, int(v))
 
+    # ---- the same over all envs at once (views of the Env array, no copy) ----
+    def _raw(self) -> np.ndarray:
+        return np.frombuffer(self.envs, dtype=np.uint8).reshape(self.n, ctypes.sizeof(Env))
+
+    def field(self, name, shape=()) -> np.ndarray:
+        """Writable view [n, *shape] of one int32 field of every env."""
+        off = getattr(Env, name).offset
+        cnt = int(np.prod(shape)) if shape else 1
+        v = self._raw()[:, off:off + 4 * cnt].view(np.int32)
+        return v.reshape((self.n,) + tuple(shape)) if shape else v[:, 0]
+
+    def boards(self) -> np.ndarray:
+        """Writable u8 view [n, OR_MAX_W, OR_MAX_H] of every env's board."""
+        off = Env.board.offset
+        return self._raw()[:, off:off + OR_MAX_W * OR_MAX_H].reshape(self.n, OR_MAX_W, OR_MAX_H)
+
+    def packed_state(self) -> dict:
+        """The engine's state layout (copies): board words [W, n] u32, piece
+        word [n] u32 (id | rot << 3 | ax << 5 | ay << 11 | lock << 17) and the
+        counter rows [13, n] i32: time, score, lines, holes, height, deaths and
+        the seven shape counts."""
+        W, H = self.cfg.width, self.cfg.height
+        f = self.field
+        assert ((f("ax") | f("ay")) >> 6 == 0).all() and (f("lock") >= 0).all()  # each in its bit field
+        piece = (f("shape_id") | (f("rot") & 3) << 3 | f("ax") << 5 | f("ay") << 11 | f("lock") << 17)
+        stats = np.stack([f(k) for k in ("time", "score", "lines_cleared", "holes", "piece_height", "n_deaths")]
+                         + list(f("counts", (7,)).T))
+        return dict(board=pack_cols(self.boards()[:, :W, :H]).T.copy(), piece=piece.astype(np.uint32), stats=stats)
+
+
+def pack_cols(board_u8) -> np.ndarray:
+    """Cells [..., W, H] -> column words [..., W] u32, bit y of word x (64-bit
+    shifts: right for every H up to 32)."""
+    b = (np.asarray(board_u8) != 0).astype(np.uint64)
+    return (b << np.arange(b.shape[-1], dtype=np.uint64)).sum(axis=-1).astype(np.uint32)
+
 
 # tetris_env.py:10-19, in shape_names order T,J,L,Z,S,I,O
 BASE_SHAPES = (

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+from harness import ParallelOracle, check_f32
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, WU, K, W, H = 2051, 3, 12, 10, 20
 
@@ -49,7 +51,6 @@ def test_plain_run_measures_the_headline_only(plain_run):
 
 @pytest.mark.gpu
 def test_dumped_outputs_equal_the_oracle(plain_run):
-    from test_gpu_long_horizon import ParallelOracle
     _, out = plain_run
     got = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
     assert sorted(got) == ["done", "obs", "obs_f32", "reward"]
@@ -66,8 +67,7 @@ def test_dumped_outputs_equal_the_oracle(plain_run):
     assert np.array_equal(got["done"], ref["done"][0].astype(np.float64))
     assert got["obs"].shape == (W, N)
     assert np.array_equal(got["obs"].T, ref["obs"][0].astype(np.float64))
-    bits = (ref["obs"][0].astype(np.uint32)[:, :, None] >> np.arange(H, dtype=np.uint32)) & 1
-    assert np.array_equal(got["obs_f32"], bits.astype(np.float32))  # [n][W][H]
+    check_f32(got["obs_f32"], ref["obs"][0], H, WU + K - 1)  # [n][W][H]
 
 
 def test_dump_outputs_samples_above_the_budget(tmp_path, monkeypatch):

@@ -23,8 +23,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_interop import Foreign
-from test_gpu_parity import _engine
+from harness import Foreign, assert_same_state, engine as _engine
 
 pytestmark = pytest.mark.gpu
 
@@ -84,12 +83,6 @@ def _same(entry, e, twin, acts, applied, what):
         assert torch.equal(g, w), (what, i)
 
 
-def _states_equal(e, twin):
-    a, b = (getattr(x, "engine", x).get_state() for x in (e, twin))
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
-
-
 @pytest.mark.parametrize("entry", ENTRIES)
 @pytest.mark.parametrize("mode", [True, "async", False], ids=["True", "async", "False"])
 def test_action_check_matrix(mode, entry):
@@ -146,7 +139,7 @@ def test_action_check_matrix(mode, entry):
             # the next good step equals the twin's: a refused call stepped nothing
             good = fresh()
             _same(entry, e, twin, torch.as_tensor(good, device=dev), good, (kind, via, "after"))
-    _states_equal(e, twin)
+    assert_same_state(e, twin)
     e.close()
     twin.close()
 
@@ -176,6 +169,6 @@ def test_action_errors_that_are_not_key_errors(mode):
         e.step_n(torch.zeros((0, N), dtype=torch.uint8, device=dev))
     good = np.arange(N) % 7
     _same("step", e, twin, torch.as_tensor(good, device=dev), good.astype(np.uint8), "after")
-    _states_equal(e, twin)
+    assert_same_state(e, twin)
     e.close()
     twin.close()

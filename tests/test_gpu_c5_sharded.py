@@ -17,11 +17,12 @@ runs the padding path of `gather_outputs` / `assemble`.
 """
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
+
+from harness import check_bench_dump, free_port
 
 pytestmark = pytest.mark.gpu
 
@@ -46,8 +47,8 @@ sh.reset()
 acts = torch.empty(sh.n, dtype=torch.uint8, device=dev)
 orc = None
 if rank == 0:
-    from test_gpu_long_horizon import ParallelOracle, _pack_board
-    orc = ParallelOracle(NG, {{}})
+    from harness import ParallelOracle, assert_same_state, check_step
+    orc = ParallelOracle(NG, {{}}, seed_base=SEED, aseed=ASEED, board=(W, H))
 t_start = time.time()
 deaths = 0
 for t0 in range(0, T, CH):
@@ -59,14 +60,11 @@ for t0 in range(0, T, CH):
         if rank == 0:
             o, r, d = sh.assemble(bufs)
             assert o.shape == (W, NG) and r.shape == (NG,) and d.shape == (NG,)
-            got.append((o.numpy().view(np.uint32).copy(), r.numpy().copy(), d.numpy().copy()))
+            got.append((o.numpy().copy(), r.numpy().copy(), d.numpy().copy()))
     if rank == 0:
         ref = orc.rollout(t0, CH)
         for i, (o, r, d) in enumerate(got):
-            assert np.array_equal(r, ref["reward"][i]), ("reward", t0 + i)
-            assert np.array_equal(d.astype(np.uint8), ref["done"][i]), ("done", t0 + i)
-            bad = np.argwhere(o.T != ref["obs"][i])
-            assert bad.size == 0, ("obs", t0 + i, bad[:4])
+            check_step(ref, i, o, r, d, at=t0 + i)
             deaths += int(d.sum())
         print("rank 0: steps %d..%d bit-exact (%.0f s)" % (t0, t0 + CH - 1, time.time() - t_start), flush=True)
 # final state of every shard, gathered to rank 0 (padded to the largest shard)
@@ -83,21 +81,11 @@ gl = [torch.empty_like(send) for _ in range(world)] if rank == 0 else None
 dist.gather(send, gather_list=gl, dst=0)
 if rank == 0:
     fin = np.concatenate([g.numpy()[:, :c] for g, c in zip(gl, sh.counts)], axis=1)
-    ref = orc.final_state()
-    brd, stats, piece, fold = fin[:W], fin[W:W + 19], fin[W + 19].astype(np.uint32), fin[W + 20].view(np.uint64)
-    assert np.array_equal(brd.astype(np.uint32), _pack_board(ref["board"])), "board"
-    for row, field in ((0, "time"), (1, "score"), (2, "lines_cleared"), (3, "holes"),
-                       (4, "piece_height"), (5, "n_deaths")):
-        assert np.array_equal(stats[row], ref[field]), field
-    assert np.array_equal(stats[6:13].T, ref["counts"]), "shape counts"
-    for name, v in (("shape_id", piece & 7), ("rot", (piece >> 3) & 3), ("ax", (piece >> 5) & 63),
-                    ("ay", (piece >> 11) & 63), ("lock", piece >> 17)):
-        assert np.array_equal(v.astype(np.int64), ref[name].astype(np.int64)), name
-    assert np.array_equal(stats[13], ref["rng"]["index"]), "MT index"
-    rmt = ref["rng"]["mt"].astype(np.uint64)
+    exp = orc.packed_state()
     with np.errstate(over="ignore"):
-        rfold = (rmt * mult).sum(axis=1, dtype=np.uint64)
-    assert np.array_equal(fold, rfold), "MT words"
+        exp["mt"] = (exp["mt"].astype(np.uint64) * mult).sum(axis=1, dtype=np.uint64)
+    assert_same_state(dict(board=fin[:W], stats=fin[W:W + 13], mt_index=fin[W + 13], piece=fin[W + 19],
+                           mt=fin[W + 20].view(np.uint64)), exp, "final state")
     assert deaths > NG // 4  # auto-resets happened inside the compared span
     orc.close()
     print("C5 OK", flush=True)
@@ -106,16 +94,10 @@ dist.destroy_process_group()
 """
 
 
-def _port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _run_ranks(tmp_path, n_global, steps, chunk, timeout):
     script = tmp_path / "c5_worker.py"
     script.write_text(WORKER.format(root=ROOT, n_global=n_global, steps=steps, chunk=chunk))
-    port = _port()
+    port = free_port()
     procs = []
     logs = []
     # rank logs under gpurun_out/ when it exists (a long run then shows progress there)
@@ -168,7 +150,6 @@ def test_bench_gpus8_direct_invocation(tmp_path):
     decode of the gathered rows (K gathers and K decodes inside the region),
     and rank 0's decoded outputs of the last timed step equal the oracle
     stepping all 8 x 2,048 envs.  Rank 0 prints one JSON line."""
-    from test_gpu_multirank import check_bench_dump
     dump = tmp_path / "c5.npz"
     env = dict(os.environ, ST_BENCH_SHARED_GPU="1", ST_BENCH_DUMP=str(dump))
     env.pop("WORLD_SIZE", None)

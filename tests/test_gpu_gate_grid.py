@@ -39,9 +39,9 @@ import numpy as np
 import pytest
 import torch
 
+from harness import (C4, assert_same_state, check_final_observation, check_info, check_step,
+                     engine as _engine, engine_state)
 from oracle import oracle as O
-from test_gpu_parity import _engine
-from test_gpu_vec_env import C4, _check_info, _unpack_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -61,15 +61,6 @@ def _positions(n):
     if n > S:
         pos += [S, S + B]
     return sorted({p for p in pos if 0 <= p < n})
-
-
-def _state(b, fields=("board", "piece", "stats", "mt")):
-    return {k: v.copy() for k, v in b.get_state(fields).items()}
-
-
-def _same_state(sa, sb, what=""):
-    for k in sa:
-        assert np.array_equal(sa[k], sb[k]), (k, what)
 
 
 @pytest.mark.parametrize("n", [B + 1, 3 * B + 1, S, S + 1, NBIG])
@@ -247,33 +238,23 @@ def test_gated_step_kernels_vs_oracle(api, kw, obs):
         if t in (40, 110):
             bad = a.clone()
             bad[n - 1 if t == 40 else 64] = 9  # the last, partly filled workgroup; a full one
-            before = _state(eng)
+            before = engine_state(eng)
             with pytest.raises(KeyError):
                 env.step(bad, obs=obs) if api == "batch" else env.step(bad)
-            _same_state(before, _state(eng), t)
+            assert_same_state(before, eng, t)
         done = ref["done"][t].astype(bool)
         robs = ref["obs"][t]  # [n][W]: the terminal obs where done
         if api == "batch":
             o, r, d = env.step(a, obs=obs)
-            packed = eng.obs if obs == "f32" else o
             if obs == "f32":
-                assert torch.equal(o, eng.obs_to_f32(packed)), ("f32 obs", t)
-            assert np.array_equal(packed.cpu().numpy().view(np.uint32).T, robs), ("obs", t)
+                assert torch.equal(o, eng.obs_to_f32(eng.obs)), ("f32 obs", t)
+            check_step(ref, t, eng.obs if obs == "f32" else o, r, d)
         else:
             o, r, d, info = env.step(a)
-            ret, fin = np.where(done[:, None], 0, robs), np.where(done[:, None], robs, 0)
-            got_fin = info["final_observation"]
-            if obs == "f32":
-                ret, fin = _unpack_f32(ret, h), _unpack_f32(fin, h)
-                got, got_fin = o.cpu().numpy(), got_fin.cpu().numpy()
-            else:
-                got, got_fin = o.cpu().numpy().view(np.uint32).T, got_fin.cpu().numpy().view(np.uint32).T
-            assert np.array_equal(got, ret), ("reset-convention obs", t)
-            assert np.array_equal(got_fin, fin), ("final_observation", t)
-            assert np.array_equal(info["_final_observation"].cpu().numpy(), done), t
-            _check_info(info, ref["stats"][t], done, t)
-        assert np.array_equal(r.cpu().numpy(), ref["reward"][t]), ("reward", t)
-        assert np.array_equal(d.cpu().numpy().astype(bool), done), ("done", t)
+            f32 = h if obs == "f32" else None
+            check_step(ref, t, o, r, d, np.where(done[:, None], 0, robs), H=f32)  # the reset convention
+            check_final_observation(info, robs, done, t, H=f32)
+            check_info(info, ref["stats"][t], done, t)
     if w * h == 16:
         assert ref["done"].sum() > n  # a 4x4 board: resets and spawns into a full board all along
     env.close()
@@ -305,7 +286,7 @@ def test_gate_covers_only_first_of_step_n():
         ob, rb, db = out
         torch.cuda.synchronize()
         assert torch.equal(o, ob) and torch.equal(r, rb) and torch.equal(d.bool(), db.bool()), what
-        _same_state(_state(a), _state(b), what)
+        assert_same_state(a, b, what)
 
     acts = [b.gen_actions(t, 5).clone() for t in range(7)]
     bad = acts[0].clone()

@@ -4,20 +4,9 @@ rollout() without a copy, and the engine's outputs export back the same way."""
 import pytest
 import torch
 
+from harness import Foreign
+
 pytestmark = pytest.mark.gpu
-
-
-class Foreign:
-    """A non-torch DLPack producer over a torch tensor's memory."""
-
-    def __init__(self, t):
-        self.t = t
-
-    def __dlpack__(self, stream=None, **kw):
-        return self.t.__dlpack__() if stream is None else self.t.__dlpack__(stream=stream)
-
-    def __dlpack_device__(self):
-        return self.t.__dlpack_device__()
 
 
 def test_dlpack_actions_zero_copy_and_equal():

@@ -20,9 +20,9 @@ import numpy as np
 import pytest
 import torch
 
+from harness import (C4, cached_ref, check_engine_state, check_step, check_steps, drive_surface,
+                     engine as _engine, pack_cols, record)
 from oracle import oracle as O
-from test_gpu_box_descriptors import C4, _field, _unpack_f32
-from test_gpu_parity import _engine
 
 T = 16
 SEED0 = 9090
@@ -96,26 +96,6 @@ def crafted_actions(n):
     return acts
 
 
-def _raw(ob):
-    return np.frombuffer(ob.envs, dtype=np.uint8).reshape(ob.n, ctypes.sizeof(O.Env))
-
-
-def _boards(ob):
-    """The oracle's boards as u8 [n, 32, 32] (a view)."""
-    off = O.Env.board.offset
-    return _raw(ob)[:, off:off + O.OR_MAX_W * O.OR_MAX_H].reshape(ob.n, O.OR_MAX_W, O.OR_MAX_H)
-
-
-def _state(ob, W, H):
-    """Board words [W, n], piece word [n] and counter rows 0..12 [13, n]."""
-    board = (_boards(ob)[:, :W, :H].astype(np.uint32) << np.arange(H, dtype=np.uint32)).sum(axis=2).T
-    piece = (_field(ob, "shape_id") | (_field(ob, "rot") & 3) << 3 | _field(ob, "ax") << 5 |
-             _field(ob, "ay") << 11 | _field(ob, "lock") << 17).astype(np.uint32)
-    stats = np.stack([_field(ob, k) for k in ("time", "score", "lines_cleared", "holes", "piece_height",
-                                              "n_deaths")] + list(_field(ob, "counts", (7,)).T))
-    return dict(board=board.astype(np.uint32), piece=piece, stats=stats.copy())
-
-
 def oracle_run(W, H, n, kw):
     """The oracle from the crafted state: its outputs of every step, its state
     at the start and after every step, which envs locked in each step, and
@@ -124,62 +104,37 @@ def oracle_run(W, H, n, kw):
     cs = crafted_state(W, H, bool(kw.get("advanced_clears")))
     ob = O.OracleBatch(n, [SEED0 + e for e in range(n)], width=W, height=H, **kw)
     ob.reset()
-    _boards(ob)[:, :W, :H] = cs["board"][:n]
+    ob.boards()[:, :W, :H] = cs["board"][:n]
     cells = np.array(O.rotate_cells(O.BASE_SHAPES[5], 0), np.int32)
-    _field(ob, "shape", (4, 2))[:] = cells
-    _field(ob, "shape_id")[:] = 5
-    _field(ob, "rot")[:] = 0
-    _field(ob, "ax")[:] = cs["c"][:n]
-    _field(ob, "ay")[:] = cs["ay"][:n]
+    ob.field("shape", (4, 2))[:] = cells
+    ob.field("shape_id")[:] = 5
+    ob.field("rot")[:] = 0
+    ob.field("ax")[:] = cs["c"][:n]
+    ob.field("ay")[:] = cs["ay"][:n]
     for k, v in cs["counters"].items():
-        _field(ob, k)[:] = v[:n]
+        ob.field(k)[:] = v[:n]
     assert np.array_equal(ob.board(n - 1), cs["board"][n - 1]) and ob.envs[n - 1].ax == cs["c"][n - 1]
     assert [tuple(x) for x in ob.envs[n - 1].shape] == [tuple(x) for x in cells]  # the views wrote through
-    start = _raw(ob).tobytes()
+    start = bytes(ob.envs)
     acts = crafted_actions(n)
-    out = dict(acts=acts, ncl=cs["ncl"][:n], init=_state(ob, W, H),
-               obs=np.empty((T, n, W), np.uint32), reward=np.empty((T, n), np.int32),
-               done=np.empty((T, n), np.uint8), stats=np.empty((T, n, 8), np.int32),
-               locked=np.empty((T, n), bool), state=[])
-    for t in range(T):
-        before = _field(ob, "counts", (7,)).sum(axis=1)
-        r = ob.rollout(acts[t:t + 1])
-        for k in ("obs", "reward", "done", "stats"):
-            out[k][t] = r[k][0]
-        out["locked"][t] = (_field(ob, "counts", (7,)).sum(axis=1) != before) | (r["done"][0] != 0)
-        out["state"].append(_state(ob, W, H))
+    init, state = ob.packed_state(), []
+    out = record(ob, acts, after=lambda t, locked, pre: state.append(ob.packed_state()))
+    out.update(ncl=cs["ncl"][:n], init=init, state=state)
     twin = O.OracleBatch(n, [0] * n, width=W, height=H, **kw)
     ctypes.memmove(ctypes.addressof(twin.envs), start, len(start))
     death_board = np.zeros((W, n), np.uint32)
     for i in np.nonzero(out["done"][0])[0]:
         _, _, d, _ = twin.step_one(int(i), int(acts[0, i]))
         assert d
-        death_board[:, i] = (twin.board(i).astype(np.uint32) << np.arange(H, dtype=np.uint32)).sum(axis=1)
+        death_board[:, i] = pack_cols(twin.board(i))
     out["death_board"] = death_board
     return out
 
 
-_REF = {}
-
-
-def _freeze(v):
-    if isinstance(v, np.ndarray):
-        v.setflags(write=False)
-    elif isinstance(v, dict):
-        for x in v.values():
-            _freeze(x)
-    elif isinstance(v, list):
-        for x in v:
-            _freeze(x)
-
-
 def _ref(W, H, scoring, **extra):
     """One oracle run per board and scoring, shared by the tests (read-only)."""
-    key = (W, H, scoring, tuple(sorted(extra.items())))
-    if key not in _REF:
-        _REF[key] = oracle_run(W, H, BOARDS[(W, H)], dict(SCORING[scoring], **extra))
-        _freeze(_REF[key])
-    return _REF[key]
+    return cached_ref(("lock_matrix", W, H, scoring, tuple(sorted(extra.items()))),
+                      lambda: oracle_run(W, H, BOARDS[(W, H)], dict(SCORING[scoring], **extra)))
 
 
 # ------------------------------------------------------------------ coverage
@@ -245,20 +200,6 @@ def _batch(board, scoring, autoreset="same_step", **extra):
     return b, ref
 
 
-def _check_state(b, exp, what="final"):
-    st = b.get_state(("board", "piece", "stats"))
-    assert np.array_equal(st["board"], exp["board"]), (what, "board")
-    assert np.array_equal(st["piece"], exp["piece"]), (what, "piece")
-    assert np.array_equal(st["stats"][:13], exp["stats"]), (what, "counters")
-
-
-def _check_step(ref, t, obs, rew, dn, robs=None):
-    assert np.array_equal(rew.cpu().numpy(), ref["reward"][t]), ("reward", t)
-    assert np.array_equal(dn.cpu().numpy().astype(np.uint8), ref["done"][t]), ("done", t)
-    robs = ref["obs"][t] if robs is None else robs
-    assert np.array_equal(obs.cpu().numpy().view(np.uint32).T, robs), ("obs", t)
-
-
 SURFACE_CASES = [((10, 20), sf, sc) for sf in ("step", "f32", "wire", "vec", "gated")
                  for sc in ("c3", "c4", "hhh")] + \
     [(bd, sf, sc) for bd in ((6, 9), (4, 4), (5, 27), (32, 28)) for sf, sc in (("step", "c4"), ("step", "hhh"),
@@ -279,51 +220,28 @@ def test_step_surfaces(board, surface, scoring):
     step_states also compares the state after each of the first three steps
     (get_state completes the MT generation and rewinds the preview, so that
     is a run of its own)."""
-    G = _engine()
-    from gym_simpletetris_amd.engine import unwire
     W, H = board
-    n = BOARDS[board]
     if surface == "vec":
         ref = _ref(W, H, scoring)
-        env = G.TetrisVecEnv(n, width=W, height=H, seed=SEED0, obs_format="packed", **SCORING[scoring])
-        env.reset()
-        b = env.engine
-        _upload(b, ref)
+        target = _engine().TetrisVecEnv(BOARDS[board], width=W, height=H, seed=SEED0, obs_format="packed",
+                                        **SCORING[scoring])
+        target.reset()
+        _upload(target.engine, ref)
     else:
-        env = None
-        b, ref = _batch(board, scoring)
+        target, ref = _batch(board, scoring)
+
+    def first_states(t):
+        if surface == "step_states" and t < 3:
+            check_engine_state(target, ref["state"][t], t)
+
     try:
-        acts = torch.as_tensor(ref["acts"].copy(), device=b.device)
-        for t in range(T):
-            done = ref["done"][t].astype(bool)
-            robs = ref["obs"][t]
-            if surface == "vec":
-                obs, rew, dn, info = env.step(acts[t])
-                fin = info["final_observation"].cpu().numpy().view(np.uint32).T
-                assert np.array_equal(fin, np.where(done[:, None], robs, 0)), ("final_observation", t)
-                st = ref["stats"][t]  # time, score, lines, holes, deaths, piece id, height, lock
-                zero = np.zeros(n, np.int32)
-                for k, col, ep in (("time", 0, "ep_time"), ("score", 1, "ep_score"),
-                                   ("lines_cleared", 2, "ep_lines"), ("holes", 3, "ep_holes")):
-                    assert np.array_equal(info[k].cpu().numpy(), np.where(done, zero, st[:, col])), (k, t)
-                    assert np.array_equal(info[ep].cpu().numpy(), np.where(done, st[:, col], zero)), (ep, t)
-                assert np.array_equal(info["deaths"].cpu().numpy(), st[:, 4]), ("deaths", t)
-                assert np.array_equal(info["piece_height"].cpu().numpy(), np.where(done, zero, st[:, 6])), t
-                robs = np.where(done[:, None], 0, robs)  # the reset convention
-            elif surface == "wire":
-                obs, rew, dn = unwire(b.step_wire(acts[t]), W, H)
-            elif surface == "f32":
-                f32, rew, dn = b.step(ref["acts"][t], obs="f32")
-                assert np.array_equal(f32.cpu().numpy(), _unpack_f32(robs, H)), ("f32 obs", t)
-                obs = b.obs
-            else:
-                obs, rew, dn = b.step(acts[t] if surface == "gated" else ref["acts"][t], obs="packed")
-            _check_step(ref, t, obs, rew, dn, robs)
-            if surface == "step_states" and t < 3:
-                _check_state(b, ref["state"][t], t)
-        _check_state(b, ref["state"][T - 1])
+        host = surface in ("step", "f32", "step_states")
+        drive_surface(target, ref, "step" if surface == "step_states" else surface,
+                      ref["acts"] if host else torch.as_tensor(ref["acts"].copy(), device=target.device),
+                      on_step=first_states)
+        check_engine_state(target, ref["state"][T - 1])
     finally:
-        (env or b).close()
+        target.close()
 
 
 @pytest.mark.gpu
@@ -336,7 +254,7 @@ def test_no_autoreset_step_then_reset(board, scoring):
     try:
         for t in range(T):
             obs, rew, dn = b.step(ref["acts"][t], obs="packed")  # (host actions: st_step ungated)
-            _check_step(ref, t, obs, rew, dn)
+            check_step(ref, t, obs, rew, dn)
             done = ref["done"][t].astype(bool)
             if t == 0:
                 assert done.any()
@@ -344,7 +262,7 @@ def test_no_autoreset_step_then_reset(board, scoring):
                 assert np.array_equal(got[:, done], ref["death_board"][:, done]), "board of a dead env"
             if done.any():
                 b.reset(torch.as_tensor(done.astype(np.uint8), device=b.device))
-        _check_state(b, ref["state"][T - 1])
+        check_engine_state(b, ref["state"][T - 1])
     finally:
         b.close()
 
@@ -359,13 +277,10 @@ def test_lock_delay(mode):
         assert ref["locked"][:6].any(axis=0).all() and not ref["locked"][:2].any()
         acts = torch.as_tensor(ref["acts"].copy(), device=b.device)
         if mode == "rollout":
-            o, rew, dn = b.rollout(acts, obs="packed")
-        for t in range(T):
-            if mode == "step":
-                _check_step(ref, t, *b.step(ref["acts"][t], obs="packed"))
-            else:
-                _check_step(ref, t, o[t], rew[t], dn[t])
-        _check_state(b, ref["state"][T - 1])
+            check_steps(ref, *b.rollout(acts, obs="packed"))
+        else:
+            drive_surface(b, ref, "step", ref["acts"])
+        check_engine_state(b, ref["state"][T - 1])
     finally:
         b.close()
 
@@ -387,17 +302,9 @@ def test_three_wave_rollout(board, scoring, obs, split):
         acts = torch.as_tensor(ref["acts"].copy(), device=b.device)
         t0 = 0
         for K in split:
-            o, rew, dn = b.rollout(acts[t0:t0 + K], obs=obs)
-            for k in range(K):
-                t = t0 + k
-                if obs == "f32":
-                    assert np.array_equal(o[k].cpu().numpy(), _unpack_f32(ref["obs"][t], H)), ("f32 obs", t)
-                    assert np.array_equal(rew[k].cpu().numpy(), ref["reward"][t]), ("reward", t)
-                    assert np.array_equal(dn[k].cpu().numpy().astype(np.uint8), ref["done"][t]), ("done", t)
-                else:
-                    _check_step(ref, t, o[k], rew[k], dn[k])
+            check_steps(ref, *b.rollout(acts[t0:t0 + K], obs=obs), t0=t0, H=H if obs == "f32" else None)
             t0 += K
-        _check_state(b, ref["state"][T - 1])
+        check_engine_state(b, ref["state"][T - 1])
     finally:
         b.close()
 
@@ -420,13 +327,8 @@ def test_two_wave_rollout(scoring):
         b.reset()
         _upload(b, ref, sel)
         acts = torch.as_tensor(ref["acts"][:K][:, sel].copy(), device=b.device)
-        o, rew, dn = b.rollout(acts, obs="packed")
-        o, rew, dn = o.cpu().numpy().view(np.uint32), rew.cpu().numpy(), dn.cpu().numpy().astype(np.uint8)
-        for t in range(K):
-            assert np.array_equal(rew[t], ref["reward"][t][sel]), ("reward", t)
-            assert np.array_equal(dn[t], ref["done"][t][sel]), ("done", t)
-            assert np.array_equal(o[t].T, ref["obs"][t][sel]), ("obs", t)
+        check_steps(ref, *b.rollout(acts, obs="packed"), sel=sel)
         exp = ref["state"][K - 1]
-        _check_state(b, dict(board=exp["board"][:, sel], piece=exp["piece"][sel], stats=exp["stats"][:, sel]))
+        check_engine_state(b, dict(board=exp["board"][:, sel], piece=exp["piece"][sel], stats=exp["stats"][:, sel]))
     finally:
         b.close()

@@ -14,67 +14,19 @@ launches of 100 steps.  The oracle runs on host threads over env slices
 (ctypes releases the GIL), so the check takes seconds.
 """
 import ctypes
-import os
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 import torch
 
+from harness import ASEED, C4, SEED_BASE, ParallelOracle, check_engine_state, mt_twist
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
 N, W, H = 65536, 10, 20
 WU, K = 100, 4000
-SEED_BASE, ASEED = 1000, 0x5EED
-CONFIGS = {
-    "c3": dict(),
-    "c4": dict(advanced_clears=True, penalise_holes_increase=True, penalise_height_increase=True),
-}
-
-
-def _threads():
-    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-    return max(1, min(16, n))
-
-
-class ParallelOracle:
-    """N oracle envs split into contiguous slices, one host thread each;
-    global env index e keeps seed SEED_BASE + e and the action stream of e."""
-
-    def __init__(self, n, kw, parts=None):
-        parts = parts or _threads()
-        bounds = np.linspace(0, n, parts + 1).astype(int)
-        self.sl = [(int(a), int(b)) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
-        kw = dict(dict(width=W, height=H), **kw)  # (a board other than 10x20: width / height in kw)
-        self.obs = [O.OracleBatch(b - a, [SEED_BASE + a + e for e in range(b - a)], **kw)
-                    for a, b in self.sl]
-        for ob in self.obs:
-            ob.reset()
-        self.pool = ThreadPoolExecutor(len(self.sl))
-
-    def rollout(self, t0, T, obs=True, stats=False):
-        def one(i):
-            a, b = self.sl[i]
-            acts = O.splitmix64_actions(ASEED, t0, T, b - a, offset=a)
-            return self.obs[i].rollout(acts, want_obs=obs, want_stats=stats)
-        rs = list(self.pool.map(one, range(len(self.sl))))
-        keys = ("reward", "done") + (("obs",) if obs else ()) + (("stats",) if stats else ())
-        return {k: np.concatenate([r[k] for r in rs], axis=1) for k in keys}
-
-    def final_state(self):
-        """Structured view of every env (Env struct fields) in global order."""
-        return np.concatenate([np.ctypeslib.as_array(ob.envs) for ob in self.obs])
-
-    def close(self):
-        self.pool.shutdown()
-
-
-def _pack_board(board_u8):
-    """oracle board [n][OR_MAX_W][OR_MAX_H] u8 -> packed columns [W][n] u32 (bit y of word x)."""
-    b = (board_u8[:, :W, :H] != 0).astype(np.uint64)
-    return (b << np.arange(H, dtype=np.uint64)).sum(axis=2).astype(np.uint32).T
+CONFIGS = {"c3": dict(), "c4": C4}
 
 
 def _seeded_words(n):
@@ -85,31 +37,12 @@ def _seeded_words(n):
     return out
 
 
-def _twist_np(w):
-    """One MT19937 refill of every row (CPython genrand_uint32 at index 624)."""
-    w = w.astype(np.uint32).copy()
-    for k in range(624):
-        y = (w[:, k] & np.uint32(0x80000000)) | (w[:, (k + 1) % 624] & np.uint32(0x7FFFFFFF))
-        w[:, k] = w[:, (k + 397) % 624] ^ (y >> np.uint32(1)) ^ np.where(y & np.uint32(1), np.uint32(0x9908B0DF),
-                                                                       np.uint32(0))
-    return w
-
-
 def _check_final(eng, orc):
-    st = eng.get_state()  # st_mt_sync first: CPython's exact MT state
-    ref = orc.final_state()
-    stats = st["stats"]
-    for row, field in ((0, "time"), (1, "score"), (2, "lines_cleared"), (3, "holes"),
-                       (4, "piece_height"), (5, "n_deaths")):
-        assert np.array_equal(stats[row], ref[field]), field
-    assert np.array_equal(stats[6:13].T, ref["counts"]), "shape counts"
-    p = st["piece"]
-    for name, got in (("shape_id", p & 7), ("rot", (p >> 3) & 3), ("ax", (p >> 5) & 63),
-                      ("ay", (p >> 11) & 63), ("lock", p >> 17)):
-        assert np.array_equal(got.astype(np.int64), ref[name].astype(np.int64)), name
-    assert np.array_equal(st["board"], _pack_board(ref["board"])), "board"
-    assert np.array_equal(stats[13], ref["rng"]["index"]), "MT index"
-    assert np.array_equal(st["mt"], ref["rng"]["mt"].astype(np.uint32)), "MT words"
+    exp = orc.packed_state()
+    check_engine_state(eng, exp)
+    st = eng.get_state(("stats", "mt"))  # st_mt_sync first: CPython's exact MT state
+    assert np.array_equal(st["stats"][13], exp["mt_index"]), "MT index"
+    assert np.array_equal(st["mt"], exp["mt"]), "MT words"
 
 
 def _compare(t0, got_r, got_d, got_o, ref):
@@ -119,6 +52,37 @@ def _compare(t0, got_r, got_d, got_o, ref):
     assert bad.size == 0, f"obs mismatch at (step, env) {bad[:4] + [t0, 0]}"
 
 
+def _bench_batch(n, kw, T):
+    """bench.py's batch of n envs on cuda:0 and T rows of its action stream
+    (generated ahead of the reset, as the bench does)."""
+    import gym_simpletetris_amd as G
+    dev = torch.device("cuda", 0)
+    eng = G.TetrisBatch(n, autoreset="same_step", seeds=[SEED_BASE + e for e in range(n)],
+                        device=dev, width=W, height=H, **kw)
+    acts = torch.empty((T, n), dtype=torch.uint8, device=dev)
+    for t in range(T):
+        eng.gen_actions(t, ASEED, out=acts[t])
+    eng.reset()
+    return eng, acts, dev
+
+
+def _st_step(eng, acts, obs, rew, done, t, sp):
+    """One st_step launch at the C ABI: step t's outputs into their own slot."""
+    from gym_simpletetris_amd import _lib as C
+    vp = ctypes.c_void_p
+    C.check(eng._L.st_step(eng._ctx, vp(acts[t].data_ptr()), vp(obs[t].data_ptr()), vp(rew[t].data_ptr()),
+                           vp(done[t].data_ptr()), sp))
+
+
+def _compare_slots(orc, obs, rew, done, CH):
+    """Every step's slot against the oracle, CH steps at a time."""
+    T = len(rew)
+    for t0 in range(0, T, CH):
+        t1 = min(t0 + CH, T)
+        _compare(t0, rew[t0:t1].cpu().numpy(), done[t0:t1].cpu().numpy(), obs[t0:t1].cpu().numpy().view(np.uint32),
+                 orc.rollout(t0, t1 - t0))
+
+
 @pytest.mark.parametrize("config,launch", [("c3", "eager"), ("c3", "graph"), ("c4", "eager")])
 def test_bench_workload_st_step(config, launch):
     """bench.py's headline region (eager: the default; graph: `--launch
@@ -126,38 +90,25 @@ def test_bench_workload_st_step(config, launch):
     case the outputs of the timed steps hold a sentinel after the capture
     (capturing runs nothing) and the oracle's values after the replay: the
     compared steps really came from the graph."""
-    import gym_simpletetris_amd as G
-    from gym_simpletetris_amd import _lib as C
-    dev = torch.device("cuda", 0)
     kw = CONFIGS[config]
-    eng = G.TetrisBatch(N, autoreset="same_step", seeds=[SEED_BASE + e for e in range(N)],
-                        device=dev, width=W, height=H, **kw)
     T = WU + K
-    acts = torch.empty((T, N), dtype=torch.uint8, device=dev)
-    for t in range(T):
-        eng.gen_actions(t, ASEED, out=acts[t])
-    eng.reset()
+    eng, acts, dev = _bench_batch(N, kw, T)
     SENT = -12345
     obs = torch.full((T, W, N), SENT, dtype=torch.int32, device=dev)
     rew = torch.full((T, N), SENT, dtype=torch.int32, device=dev)
     done = torch.full((T, N), 7, dtype=torch.uint8, device=dev)
     torch.cuda.synchronize(dev)
-    L, ctx = eng._L, eng._ctx
     s = torch.cuda.Stream(dev)
     sp = ctypes.c_void_p(s.cuda_stream)
-
-    def launch_step(t):
-        C.check(L.st_step(ctx, ctypes.c_void_p(acts[t].data_ptr()), ctypes.c_void_p(obs[t].data_ptr()),
-                          ctypes.c_void_p(rew[t].data_ptr()), ctypes.c_void_p(done[t].data_ptr()), sp))
     with torch.cuda.stream(s):
         for t in range(WU):  # bench warm-up: eager launches
-            launch_step(t)
+            _st_step(eng, acts, obs, rew, done, t, sp)
     torch.cuda.synchronize(dev)
     if launch == "graph":
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=s):  # bench --launch graph: one graph of K launches
             for t in range(WU, T):
-                launch_step(t)
+                _st_step(eng, acts, obs, rew, done, t, sp)
         torch.cuda.synchronize(dev)
         # captured, not run: every timed step's outputs still hold the sentinel
         assert bool((rew[WU:] == SENT).all()) and bool((obs[WU:] == SENT).all()) and bool((done[WU:] == 7).all())
@@ -169,20 +120,16 @@ def test_bench_workload_st_step(config, launch):
         assert launch == "eager"
         with torch.cuda.stream(s):  # bench default: K eager launches
             for t in range(WU, T):
-                launch_step(t)
+                _st_step(eng, acts, obs, rew, done, t, sp)
         torch.cuda.synchronize(dev)
     assert not bool((rew == SENT).any()) and not bool((done == 7).any())
     orc = ParallelOracle(N, kw)
     try:
-        CH = 100
-        for t0 in range(0, T, CH):
-            ref = orc.rollout(t0, CH)
-            _compare(t0, rew[t0:t0 + CH].cpu().numpy(), done[t0:t0 + CH].cpu().numpy(),
-                     obs[t0:t0 + CH].cpu().numpy().view(np.uint32), ref)
+        _compare_slots(orc, obs, rew, done, 100)
         _check_final(eng, orc)
         # the regime the bench times: most envs went past their first generation
         fin = orc.final_state()["rng"]["mt"].astype(np.uint32)
-        gen1 = _twist_np(_seeded_words(N))
+        gen1 = mt_twist(_seeded_words(N))
         assert (fin != gen1).any(axis=1).mean() > 0.5
     finally:
         orc.close()
@@ -194,33 +141,19 @@ def test_c2_shape_eager_long():
     rewards, same-step auto-reset, 1,200 eager st_step launches (one per
     step, as bench.py times C2), every step's reward / done / packed obs and
     the final state bit-exact against the oracle."""
-    import gym_simpletetris_amd as G
-    from gym_simpletetris_amd import _lib as C
     n, T = 4096, 1200
-    dev = torch.device("cuda", 0)
-    eng = G.TetrisBatch(n, autoreset="same_step", seeds=[SEED_BASE + e for e in range(n)],
-                        device=dev, width=W, height=H)
-    acts = torch.empty((T, n), dtype=torch.uint8, device=dev)
-    for t in range(T):
-        eng.gen_actions(t, ASEED, out=acts[t])
-    eng.reset()
+    eng, acts, dev = _bench_batch(n, {}, T)
     obs = torch.empty((T, W, n), dtype=torch.int32, device=dev)
     rew = torch.empty((T, n), dtype=torch.int32, device=dev)
     done = torch.empty((T, n), dtype=torch.uint8, device=dev)
     torch.cuda.synchronize(dev)
-    L, ctx = eng._L, eng._ctx
     sp = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     for t in range(T):
-        C.check(L.st_step(ctx, ctypes.c_void_p(acts[t].data_ptr()), ctypes.c_void_p(obs[t].data_ptr()),
-                          ctypes.c_void_p(rew[t].data_ptr()), ctypes.c_void_p(done[t].data_ptr()), sp))
+        _st_step(eng, acts, obs, rew, done, t, sp)
     torch.cuda.synchronize(dev)
     orc = ParallelOracle(n, {})
     try:
-        CH = 200
-        for t0 in range(0, T, CH):
-            ref = orc.rollout(t0, CH)
-            _compare(t0, rew[t0:t0 + CH].cpu().numpy(), done[t0:t0 + CH].cpu().numpy(),
-                     obs[t0:t0 + CH].cpu().numpy().view(np.uint32), ref)
+        _compare_slots(orc, obs, rew, done, 200)
         _check_final(eng, orc)
         assert int(done.sum()) > n  # episodes turned over inside the compared span
     finally:
@@ -228,19 +161,11 @@ def test_c2_shape_eager_long():
         eng.close()
 
 
-@pytest.mark.parametrize("config", sorted(CONFIGS))
-def test_bench_workload_st_rollout(config):
-    import gym_simpletetris_amd as G
-    dev = torch.device("cuda", 0)
-    kw = CONFIGS[config]
-    eng = G.TetrisBatch(N, autoreset="same_step", seeds=[SEED_BASE + e for e in range(N)],
-                        device=dev, width=W, height=H, **kw)
-    CH, NL = 100, 10
-    acts = torch.empty((CH * NL, N), dtype=torch.uint8, device=dev)
-    for t in range(CH * NL):
-        eng.gen_actions(t, ASEED, out=acts[t])
-    eng.reset()
-    orc = ParallelOracle(N, kw)
+def _rollouts_vs_oracle(n, kw, CH, NL):
+    """NL st_rollout launches of CH steps: every step's outputs and the final
+    state against the oracle."""
+    eng, acts, _ = _bench_batch(n, kw, CH * NL)
+    orc = ParallelOracle(n, kw)
     buf = {}
     try:
         for c in range(NL):
@@ -251,6 +176,11 @@ def test_bench_workload_st_rollout(config):
     finally:
         orc.close()
         eng.close()
+
+
+@pytest.mark.parametrize("config", sorted(CONFIGS))
+def test_bench_workload_st_rollout(config):
+    _rollouts_vs_oracle(N, CONFIGS[config], 100, 10)
 
 
 @pytest.mark.parametrize("config", sorted(CONFIGS))
@@ -259,30 +189,10 @@ def test_rollout_large_batch_two_wave_kernel(config):
     (launch_rollout's choice; the three-wave kernel below it): 2x the CUs'
     4-workgroup batch plus a ragged tail, 3 launches x 100 steps, every step's
     outputs and the final state bit-exact against the oracle."""
-    import gym_simpletetris_amd as G
-    dev = torch.device("cuda", 0)
-    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
     n = 2 * 4 * 64 * cus + 37
     assert n > 4 * 64 * cus
-    kw = CONFIGS[config]
-    eng = G.TetrisBatch(n, autoreset="same_step", seeds=[SEED_BASE + e for e in range(n)],
-                        device=dev, width=W, height=H, **kw)
-    CH, NL = 100, 3
-    acts = torch.empty((CH * NL, n), dtype=torch.uint8, device=dev)
-    for t in range(CH * NL):
-        eng.gen_actions(t, ASEED, out=acts[t])
-    eng.reset()
-    orc = ParallelOracle(n, kw)
-    buf = {}
-    try:
-        for c in range(NL):
-            o, r, d = eng.rollout(acts[c * CH:(c + 1) * CH], obs="packed", out=buf)
-            ref = orc.rollout(c * CH, CH)
-            _compare(c * CH, r.cpu().numpy(), d.cpu().numpy(), o.cpu().numpy().view(np.uint32), ref)
-        _check_final(eng, orc)
-    finally:
-        orc.close()
-        eng.close()
+    _rollouts_vs_oracle(n, CONFIGS[config], 100, 3)
 
 
 @pytest.mark.parametrize("n,steps", [(65537, 600), (1 << 20, 24)])
@@ -290,40 +200,24 @@ def test_ragged_and_large_batches(n, steps):
     """A ragged batch (65,537 envs: the last wave holds one real env, the
     stride is padded) over 600 graph-replayed steps, and 2^20 envs (16x the
     headline batch) over 24 steps, both bit-exact vs the oracle, C4 scoring."""
-    import gym_simpletetris_amd as G
-    from gym_simpletetris_amd import _lib as C
-    dev = torch.device("cuda", 0)
     kw = CONFIGS["c4"]
-    eng = G.TetrisBatch(n, autoreset="same_step", seeds=[SEED_BASE + e for e in range(n)],
-                        device=dev, width=W, height=H, **kw)
-    acts = torch.empty((steps, n), dtype=torch.uint8, device=dev)
-    for t in range(steps):
-        eng.gen_actions(t, ASEED, out=acts[t])
-    eng.reset()
+    eng, acts, dev = _bench_batch(n, kw, steps)
     obs = torch.empty((steps, W, n), dtype=torch.int32, device=dev)
     rew = torch.empty((steps, n), dtype=torch.int32, device=dev)
     done = torch.empty((steps, n), dtype=torch.uint8, device=dev)
     torch.cuda.synchronize(dev)
-    L, ctx = eng._L, eng._ctx
     s = torch.cuda.Stream(dev)
-    sp = ctypes.c_void_p(s.cuda_stream)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=s):
         for t in range(steps):
-            C.check(L.st_step(ctx, ctypes.c_void_p(acts[t].data_ptr()), ctypes.c_void_p(obs[t].data_ptr()),
-                              ctypes.c_void_p(rew[t].data_ptr()), ctypes.c_void_p(done[t].data_ptr()), sp))
+            _st_step(eng, acts, obs, rew, done, t, ctypes.c_void_p(s.cuda_stream))
     with torch.cuda.stream(s):
         g.replay()
     torch.cuda.synchronize(dev)
     del g
     orc = ParallelOracle(n, kw)
     try:
-        CH = 100
-        for t0 in range(0, steps, CH):
-            T = min(CH, steps - t0)
-            ref = orc.rollout(t0, T)
-            _compare(t0, rew[t0:t0 + T].cpu().numpy(), done[t0:t0 + T].cpu().numpy(),
-                     obs[t0:t0 + T].cpu().numpy().view(np.uint32), ref)
+        _compare_slots(orc, obs, rew, done, 100)
         _check_final(eng, orc)
     finally:
         orc.close()
@@ -357,10 +251,10 @@ def test_soak_many_generations():
         _check_final(eng, orc)
         assert deaths > 1000 * n  # the episodes really turned over
         fin = orc.final_state()["rng"]["mt"].astype(np.uint32)
-        gen = _twist_np(_seeded_words(n))
+        gen = mt_twist(_seeded_words(n))
         for _ in range(12):  # far past them: none of the first twelve generations remains
             assert not (fin == gen).all(axis=1).any()
-            gen = _twist_np(gen)
+            gen = mt_twist(gen)
     finally:
         orc.close()
         eng.close()

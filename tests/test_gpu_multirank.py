@@ -11,13 +11,14 @@
 """
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
+
+from harness import check_bench_dump, free_port
 
 pytestmark = pytest.mark.gpu
 
@@ -52,18 +53,12 @@ dist.destroy_process_group()
 """
 
 
-def _port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def test_two_ranks_gather_equals_one_batch(tmp_path):
     out = str(tmp_path / "gathered.npz")
     script = tmp_path / "worker.py"
     script.write_text(WORKER.format(root=ROOT, n_global=2 * N_LOCAL + 1, seed=SEED, steps=T, aseed=ASEED,
                                     out=out))
-    port = _port()
+    port = free_port()
     procs = []
     for r in range(2):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r),
@@ -84,27 +79,6 @@ def test_two_ranks_gather_equals_one_batch(tmp_path):
         assert np.array_equal(d.cpu().numpy().astype(np.uint8), got["done"][t]), t
         assert np.array_equal(o.cpu().numpy(), got["obs"][t]), t
     assert got["done"].any()  # auto-resets happened inside the compared span
-
-
-def check_bench_dump(path, n_global, steps):
-    """bench.py's C5 region (ST_BENCH_DUMP): rank 0's assembled outputs of the
-    last timed step -- gathered from every rank -- against the oracle stepping
-    all n_global envs through the same `steps` action rows (seeds 1000 + e,
-    the bench's splitmix64 actions keyed by the global index)."""
-    from test_gpu_long_horizon import ParallelOracle
-    z = np.load(path)
-    assert int(z["n_global"]) == n_global and int(z["step"]) == steps - 1
-    orc = ParallelOracle(n_global, {})
-    try:
-        if steps > 1:
-            orc.rollout(0, steps - 1, obs=False)
-        ref = orc.rollout(steps - 1, 1)
-    finally:
-        orc.close()
-    assert np.array_equal(z["reward"], ref["reward"][0])
-    assert np.array_equal(z["done"].astype(np.uint8), ref["done"][0])
-    assert np.array_equal(z["obs"].T, ref["obs"][0])
-    return z
 
 
 def test_bench_gpus2_direct_invocation(tmp_path):
@@ -137,7 +111,7 @@ def test_bench_rccl_calls_one_rank(tmp_path):
     gather of the C5 region, at one rank (two ranks cannot share a GPU under
     RCCL); the gathered outputs of the last timed step equal the oracle's."""
     env = dict(os.environ, ST_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
-               MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_port()), ST_BENCH_DUMP=str(tmp_path / "c5.npz"))
+               MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), ST_BENCH_DUMP=str(tmp_path / "c5.npz"))
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "nccl", "--full",
                         "--steps", "30", "--warmup", "5", "--n-envs", "8192", "--no-cpu-baseline",
                         "--no-clear-heavy"],

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from harness import (C4, assert_same_state, batch_and_oracle, check_mt_state, check_step, check_steps,
+                     engine as _engine, engine_state, mt_twist, set_mt_state, unpack_f32, words)
 from oracle import oracle as O
 from replay import GOLDEN, load_set, replay_crafted, replay_rollout
 
@@ -17,11 +19,6 @@ ROLL = load_set("rollouts.npz")
 GREEDY = load_set("greedy.npz")
 CRAFTED = load_set("crafted.npz")
 RENDER = load_set("render.npz")
-
-
-def _engine():
-    import gym_simpletetris_amd as G
-    return G
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -60,7 +57,7 @@ class HipAdapter:
         return dict(reward=rew.cpu().numpy(), done=done.cpu().numpy().astype(np.uint8),
                     time=s[0], score=s[1], lines=s[2], holes=s[3], height=s[4], deaths=s[5],
                     counts=s[6:13].T, piece=st["piece"],
-                    obs=obs.cpu().numpy().view(np.uint32).T, board=st["board"].T)
+                    obs=words(obs), board=st["board"].T)
 
 
 def test_library_is_the_hip_build():
@@ -72,15 +69,6 @@ def test_library_is_the_hip_build():
     b.reset()
     b.step(np.zeros(3, np.uint8))
     torch.cuda.synchronize()
-
-
-def _twist(words):
-    """One MT19937 generation refill (CPython genrand_uint32 at index 624)."""
-    w = [int(x) for x in words]
-    for k in range(624):
-        y = (w[k] & 0x80000000) | (w[(k + 1) % 624] & 0x7FFFFFFF)
-        w[k] = w[(k + 397) % 624] ^ (y >> 1) ^ (0x9908B0DF if y & 1 else 0)
-    return np.array(w, dtype=np.uint32)
 
 
 def test_device_mt19937_matches_cpython():
@@ -104,7 +92,7 @@ def test_device_mt19937_matches_cpython():
         cp = random.Random(s).getstate()[1]
         assert np.array_equal(mt[i], np.array(cp[:624], np.uint32)), f"seed {s}"
         assert int(st["stats"][13, i]) == cp[624] == 624
-        assert np.array_equal(temper(_twist(mt[i])), d["words"][i][:624]), f"seed {s}"
+        assert np.array_equal(temper(mt_twist(mt[i][None])[0]), d["words"][i][:624]), f"seed {s}"
     # and the engine draws from it: reset + a few steps against the oracle
     b.reset()
     ob = O.OracleBatch(len(seeds), seeds)
@@ -112,12 +100,8 @@ def test_device_mt19937_matches_cpython():
     acts = np.full((30, len(seeds)), 2, np.uint8)
     ref = ob.rollout(acts)
     for t in range(30):
-        obs, rew, done = b.step(torch.as_tensor(acts[t], device=b.device))
-        assert np.array_equal(obs.cpu().numpy().view(np.uint32).T, ref["obs"][t]), t
-    fin = b.get_state(("mt", "stats"))
-    for i in range(len(seeds)):
-        assert int(fin["stats"][13, i]) == ob.envs[i].rng.index
-        assert np.array_equal(fin["mt"][i], np.ctypeslib.as_array(ob.envs[i].rng.mt))
+        check_step(ref, t, *b.step(torch.as_tensor(acts[t], device=b.device)))
+    check_mt_state(b, ob)
 
 
 @pytest.mark.parametrize("name", sorted(CRAFTED))
@@ -140,28 +124,20 @@ def test_hip_greedy_rollouts(name):
 
 def _oracle_vs_hip(n, steps, kw, seed_base=7, action_seed=99, autoreset="none"):
     """Full-size bit-exact check against the C oracle on splitmix64 actions."""
-    G = _engine()
-    b = G.TetrisBatch(n, autoreset=autoreset, seeds=[seed_base + e for e in range(n)], **kw)
-    b.reset()
-    ob = O.OracleBatch(n, [seed_base + e for e in range(n)], **kw)
-    ob.reset()
+    b, ob = batch_and_oracle(n, [seed_base + e for e in range(n)], autoreset, **kw)
     acts = O.splitmix64_actions(action_seed, 0, steps, n)
     ref = ob.rollout(acts)
     for t in range(steps):
         a = b.gen_actions(t, action_seed)
         assert np.array_equal(a.cpu().numpy(), acts[t])
         obs, rew, done = b.step(a, obs="packed")
-        assert np.array_equal(rew.cpu().numpy(), ref["reward"][t]), f"reward t={t}"
-        d = done.cpu().numpy()
-        assert np.array_equal(d.astype(np.uint8), ref["done"][t]), f"done t={t}"
-        assert np.array_equal(obs.cpu().numpy().view(np.uint32).T, ref["obs"][t]), f"obs t={t}"
-        if autoreset == "none" and d.any():
-            b.reset(torch.as_tensor(d.astype(np.uint8), device=b.device))
+        check_step(ref, t, obs, rew, done)
+        if autoreset == "none" and ref["done"][t].any():
+            b.reset(torch.as_tensor(ref["done"][t], device=b.device))
     return ref
 
 
-@pytest.mark.parametrize("kw", [dict(), dict(advanced_clears=True, penalise_holes_increase=True,
-                                             penalise_height_increase=True)])
+@pytest.mark.parametrize("kw", [dict(), C4])
 def test_hip_vs_oracle_full_size(kw):
     """N = 65,536 (BASELINE configs C3/C4) bit-exact vs the oracle, 48 steps."""
     _oracle_vs_hip(65536, 48, dict(width=10, height=20, **kw))
@@ -273,8 +249,7 @@ def test_fused_f32_obs_equals_unpacked():
             f32, rew, done = b.step(b.gen_actions(t, 3), obs="f32")
             ref = b.obs_to_f32(b.obs)
             assert torch.equal(f32, ref), (W, H, t)
-            bits = ((b.obs.cpu().numpy().view(np.uint32).T[:, :, None] >> np.arange(H)) & 1)
-            assert np.array_equal(ref.cpu().numpy(), bits.astype(np.float32))
+            assert np.array_equal(ref.cpu().numpy(), unpack_f32(words(b.obs), H))
 
 
 def test_grayscale_kernel_matches_reference_images():
@@ -329,10 +304,8 @@ def test_image_kernels_ragged_batches(n):
         b.reset()
         for t in range(30):
             b.step(b.gen_actions(t, 9))
-        cols = b.obs.cpu().numpy().view(np.uint32).T.astype(np.uint64)   # [n][W]
-        f32 = b.obs_to_f32().cpu().numpy()
-        ref = ((cols[:, :, None] >> np.arange(H, dtype=np.uint64)) & 1).astype(np.float32)
-        assert np.array_equal(f32, ref), (W, H)
+        cols = words(b.obs).astype(np.uint64)   # [n][W]
+        assert np.array_equal(b.obs_to_f32().cpu().numpy(), unpack_f32(cols, H)), (W, H)
         for size in sizes:
             exp = _image_np(cols, W, H, size)
             for ch in (1, 3):
@@ -365,8 +338,7 @@ def test_single_env_surface_vs_reference(name, rng):
     for t in range(min(300, arrs["actions"].shape[0])):
         o, r, d, info = env.step(int(arrs["actions"][t, 0]))
         assert o.shape == (W, H) and o.dtype == np.float32
-        bits = ((arrs["obs"][t, 0][:, None] >> np.arange(H)) & 1).astype(np.float32)
-        assert np.array_equal(o, bits), t
+        assert np.array_equal(o, unpack_f32(arrs["obs"][t, 0], H)), t
         assert r == arrs["reward"][t, 0] and type(r) is types[int(arrs["rtype"][t, 0])], \
             (t, r, type(r), arrs["rtype"][t, 0])
         assert d == bool(arrs["done"][t, 0])
@@ -464,22 +436,21 @@ def test_export_env_any_env_every_part():
         rec = torch.zeros(nw, dtype=torch.int32, device=b.device)
         C.check(L.st_export_env(ctx, env, P(o), P(r), P(d), C.EXPORT_MT | C.EXPORT_OBS_F32, P(rec), sp))
         recs[env] = rec.cpu().numpy()
-    words = o.cpu().numpy().view(np.uint32)
+    cols = o.cpu().numpy().view(np.uint32)
     rew, done = r.cpu().numpy(), d.cpu().numpy()
     st = b.get_state(("stats", "mt"))  # st_mt_sync: the canonical form the export computed read-only
     m = W + 2 + C.NSTAT
     for env, rec in recs.items():
-        assert np.array_equal(rec[:W].view(np.uint32), words[:, env]), env
+        assert np.array_equal(rec[:W].view(np.uint32), cols[:, env]), env
         assert rec[W] == rew[env] and rec[W + 1] == int(done[env]), env
         assert np.array_equal(rec[W + 2:m], st["stats"][:, env]), env
         assert np.array_equal(rec[m:m + C.MT_N].view(np.uint32), st["mt"][env]), env
         f32 = rec[m + C.MT_N:].view(np.float32).reshape(W, H)
-        bits = ((words[:, env][:, None].astype(np.uint64) >> np.arange(H, dtype=np.uint64)) & 1).astype(np.float32)
-        assert np.array_equal(f32, bits), env
+        assert np.array_equal(f32, unpack_f32(cols[:, env], H)), env
     rec = torch.full((nw,), -7, dtype=torch.int32, device=b.device)
     C.check(L.st_export_env(ctx, 5, P(o), P(r), P(d), 0, P(rec), sp))
     h = rec.cpu().numpy()
-    assert (h[m:] == -7).all() and np.array_equal(h[:W].view(np.uint32), words[:, 5])
+    assert (h[m:] == -7).all() and np.array_equal(h[:W].view(np.uint32), cols[:, 5])
     for env, parts in ((n, 0), (-1, 0), (0, 4)):
         with pytest.raises(C.StError):
             C.check(L.st_export_env(ctx, env, P(o), P(r), P(d), parts, P(rec), sp))
@@ -700,7 +671,7 @@ def test_rollout_equals_steps(autoreset, board, scoring):
     n, K = 1000, 150
     kw = dict(width=W, height=H, lock_delay=1, step_reset=True)
     if scoring == "penalties":
-        kw.update(penalise_holes_increase=True, advanced_clears=True, penalise_height_increase=True)
+        kw.update(C4)
     a = G.TetrisBatch(n, autoreset=autoreset, seeds=[3 + e for e in range(n)], **kw)
     b = G.TetrisBatch(n, autoreset=autoreset, seeds=[3 + e for e in range(n)], **kw)
     a.reset()
@@ -712,9 +683,7 @@ def test_rollout_equals_steps(autoreset, board, scoring):
             so, sr, sd = a.step(acts[t], obs=obs_mode)
             assert torch.equal(so, ro[t]), (obs_mode, t)
             assert torch.equal(sr, rr[t]) and torch.equal(sd, rd[t]), (obs_mode, t)
-        sa, sb = a.get_state(), b.get_state()
-        for k in sa:
-            assert np.array_equal(sa[k], sb[k]), (obs_mode, k)
+        assert_same_state(a, b, obs_mode)
 
 
 @pytest.mark.parametrize("autoreset", ["same_step", "none"])
@@ -747,26 +716,16 @@ def test_rollout_short_launches_queue_edges(autoreset):
                 assert torch.equal(so, ro[j]), (rep, t, j)
                 assert torch.equal(sr, rr[j]) and torch.equal(sd, rd[j]), (rep, t, j)
             t += k
-        sa, sb = a.get_state(), b.get_state()  # synced: no preview in either afterwards
-        for key in sa:
-            assert np.array_equal(sa[key], sb[key]), (rep, key)
+        assert_same_state(a, b, rep)  # synced: no preview in either afterwards
 
 
 def test_rollout_vs_oracle_full_size():
     """N = 65,536, K = 32 steps in one launch vs the C oracle."""
-    G = _engine()
     n, K, seed_a = 65536, 32, 99
-    kw = dict(width=10, height=20)
-    b = G.TetrisBatch(n, autoreset="same_step", seeds=[7 + e for e in range(n)], **kw)
-    b.reset()
-    ob = O.OracleBatch(n, [7 + e for e in range(n)], **kw)
-    ob.reset()
+    b, ob = batch_and_oracle(n, [7 + e for e in range(n)], width=10, height=20)
     acts = O.splitmix64_actions(seed_a, 0, K, n)
     ref = ob.rollout(acts)
-    obs, rew, done = b.rollout(torch.as_tensor(acts, device=b.device))
-    assert np.array_equal(rew.cpu().numpy(), ref["reward"])
-    assert np.array_equal(done.cpu().numpy().astype(np.uint8), ref["done"])
-    assert np.array_equal(obs.cpu().numpy().view(np.uint32).transpose(0, 2, 1), ref["obs"])
+    check_steps(ref, *b.rollout(torch.as_tensor(acts, device=b.device)))
 
 
 def _untemper(y):
@@ -794,12 +753,8 @@ def test_long_rejection_runs_and_twists(mode):
     half of the 16-word prefetch), 20 (past it: the dependent-load loop), and
     states 1-3 words from a generation's end whose successor is not built
     (host-written state: finished cooperatively), against the oracle."""
-    G = _engine()
     n, T = 64, 40
-    b = G.TetrisBatch(n, autoreset="same_step", seeds=range(n))
-    b.reset()
-    ob = O.OracleBatch(n, list(range(n)))
-    ob.reset()
+    b, ob = batch_and_oracle(n, range(n))
     st = b.get_state(("mt", "stats"))
     mt, stats = st["mt"].copy(), st["stats"].copy()
     rej, acc = _untemper(0xFFFFFFFF), _untemper(0)
@@ -819,28 +774,17 @@ def test_long_rejection_runs_and_twists(mode):
         elif i % 4 == 3 and idx + 11 <= 624:         # 10 rejections: the second prefetched half
             mt[i, idx:idx + 10] = rej
             mt[i, idx + 10] = acc
-        e = ob.envs[i]
-        for k in range(624):
-            e.rng.mt[k] = int(mt[i, k])
-        e.rng.index = int(stats[13, i])
+    set_mt_state(ob, mt, stats[13])
     b.set_state(mt=mt, stats=stats)
     acts = np.full((T, n), 2, np.uint8)              # hard drops: a lock every step
     acts[::3] = O.splitmix64_actions(5, 0, T, n)[::3]
     ref = ob.rollout(acts)
     if mode == "step":
         for t in range(T):
-            obs, rew, done = b.step(torch.as_tensor(acts[t], device=b.device))
-            assert np.array_equal(rew.cpu().numpy(), ref["reward"][t]), t
-            assert np.array_equal(obs.cpu().numpy().view(np.uint32).T, ref["obs"][t]), t
+            check_step(ref, t, *b.step(torch.as_tensor(acts[t], device=b.device)))
     else:
-        obs, rew, done = b.rollout(torch.as_tensor(acts, device=b.device))
-        assert np.array_equal(rew.cpu().numpy(), ref["reward"])
-        assert np.array_equal(done.cpu().numpy().astype(np.uint8), ref["done"])
-        assert np.array_equal(obs.cpu().numpy().view(np.uint32).transpose(0, 2, 1), ref["obs"])
-    fin = b.get_state(("mt", "stats"))
-    for i in range(n):
-        assert int(fin["stats"][13, i]) == ob.envs[i].rng.index, i
-        assert np.array_equal(fin["mt"][i], np.ctypeslib.as_array(ob.envs[i].rng.mt)), i
+        check_steps(ref, *b.rollout(torch.as_tensor(acts, device=b.device)))
+    check_mt_state(b, ob)
 
 
 def test_mt_generations_across_steps():
@@ -866,13 +810,11 @@ def test_mt_generations_across_steps():
     saw_lazy = False
     for c0 in range(0, T, chunk):
         da = torch.as_tensor(acts[c0:c0 + chunk], device=a.device)
-        oa, ra, _ = a.rollout(da)
+        oa, ra, dna = a.rollout(da)
         for t in range(c0, c0 + chunk):
             ob_, rb, _ = b.step(da[t - c0])
             assert torch.equal(ob_, oa[t - c0]) and torch.equal(rb, ra[t - c0]), t
-        assert np.array_equal(ra.cpu().numpy(), ref["reward"][c0:c0 + chunk]), c0
-        assert np.array_equal(oa.cpu().numpy().view(np.uint32).transpose(0, 2, 1),
-                              ref["obs"][c0:c0 + chunk]), c0
+        check_steps(ref, oa, ra, dna, t0=c0)
         # raw (unsynced) index row of b: some envs mid-generation
         raw = torch.empty(b.stride, dtype=torch.int32, device=b.device)
         v = b._views
@@ -883,12 +825,8 @@ def test_mt_generations_across_steps():
         if (c0 // chunk) % 3 == 1:
             a.get_state(("mt", "stats"))                # sync a only, mid-run
     assert saw_lazy
-    fa, fb = a.get_state(), b.get_state()
-    for k in fa:
-        assert np.array_equal(fa[k], fb[k]), k
-    for i in range(n):
-        assert int(fa["stats"][13, i]) == ob.envs[i].rng.index, i
-        assert np.array_equal(fa["mt"][i], np.ctypeslib.as_array(ob.envs[i].rng.mt)), i
+    assert_same_state(a, b)
+    check_mt_state(a, ob)
 
 
 @pytest.mark.parametrize("mode", ["step", "rollout"])
@@ -898,22 +836,14 @@ def test_sync_at_generation_boundary(mode):
     drawn right after it starts at 624 and runs into the next generation.
     st_mt_sync must give back exactly (old words, 624), and stepping on from
     the synced state must match the oracle."""
-    G = _engine()
     n = 64
-    b = G.TetrisBatch(n, autoreset="same_step", seeds=range(100, 100 + n))
-    b.reset()
-    ob = O.OracleBatch(n, list(range(100, 100 + n)))
-    ob.reset()
+    b, ob = batch_and_oracle(n, range(100, 100 + n))
     st = b.get_state(("mt", "stats"))
     mt, stats = st["mt"].copy(), st["stats"].copy()
     acc = _untemper(0)                  # accepted by any randint range
-    for i in range(n):
-        mt[i, 623] = acc
-        stats[13, i] = 623
-        e = ob.envs[i]
-        for k in range(624):
-            e.rng.mt[k] = int(mt[i, k])
-        e.rng.index = 623
+    mt[:, 623] = acc
+    stats[13] = 623
+    set_mt_state(ob, mt, stats[13])
     b.set_state(mt=mt, stats=stats)
     acts = np.full((1, n), 2, np.uint8)  # hard drop: every env locks and spawns
     ref = ob.rollout(acts)
@@ -932,13 +862,8 @@ def test_sync_at_generation_boundary(mode):
     acts[::2] = 2
     ref = ob.rollout(acts)
     for t in range(80):
-        obs, rew, _ = b.step(torch.as_tensor(acts[t], device=b.device))
-        assert np.array_equal(rew.cpu().numpy(), ref["reward"][t]), t
-        assert np.array_equal(obs.cpu().numpy().view(np.uint32).T, ref["obs"][t]), t
-    fin = b.get_state(("mt", "stats"))
-    for i in range(n):
-        assert int(fin["stats"][13, i]) == ob.envs[i].rng.index, i
-        assert np.array_equal(fin["mt"][i], np.ctypeslib.as_array(ob.envs[i].rng.mt)), i
+        check_step(ref, t, *b.step(torch.as_tensor(acts[t], device=b.device)))
+    check_mt_state(b, ob)
 
 
 def test_preview_rewind_across_generations():
@@ -951,25 +876,18 @@ def test_preview_rewind_across_generations():
     draws its piece, then a new preview, and the games must not change."""
     import ctypes
     from gym_simpletetris_amd import _lib as C
-    G = _engine()
     n, T = 512, 1600
-    seeds = [7000 + e for e in range(n)]
-    b = G.TetrisBatch(n, autoreset="same_step", seeds=seeds)
-    b.reset()
-    ob = O.OracleBatch(n, seeds)
-    ob.reset()
+    b, ob = batch_and_oracle(n, [7000 + e for e in range(n)])
     acts = np.full((T, n), 2, np.uint8)              # hard drops: a draw every step
     acts[::5] = O.splitmix64_actions(11, 0, T, n)[::5]
     raw = torch.empty(b.stride, dtype=torch.int32, device=b.device)
     v = b._views
-    syncs, stop, boundary = 0, T, 0
+    syncs, stop = 0, T
     for t in range(T):
         if t >= stop:
             break
-        o, r, _ = b.step(torch.as_tensor(acts[t], device=b.device))
-        ref = ob.rollout(acts[t:t + 1])
-        assert np.array_equal(r.cpu().numpy(), ref["reward"][0]), t
-        assert np.array_equal(o.cpu().numpy().view(np.uint32).T, ref["obs"][0]), t
+        out = b.step(torch.as_tensor(acts[t], device=b.device))
+        check_step(ob.rollout(acts[t:t + 1]), 0, *out, at=t)
         C.check(b._L.st_copy(ctypes.c_void_p(raw.data_ptr()),
                              ctypes.c_void_p(v.stats + C.STAT["mt_index"] * v.stride * 4),
                              raw.numel() * 4, b._stream()))
@@ -977,11 +895,7 @@ def test_preview_rewind_across_generations():
         ok = ((w >> 24) & 1).astype(bool)
         straddle = ok & ((w & 0x3FF) < ((w >> 25) & 63))
         if straddle.any() and syncs < 3:
-            st = b.get_state(("mt", "stats"))          # st_mt_sync
-            for i in range(n):  # exactly random.getstate(): words and index (624 included)
-                assert int(st["stats"][13, i]) == ob.envs[i].rng.index, (t, i)
-                assert np.array_equal(st["mt"][i], np.ctypeslib.as_array(ob.envs[i].rng.mt)), (t, i)
-                boundary += int(st["stats"][13, i]) == 624
+            check_mt_state(b, ob, t)  # st_mt_sync: exactly random.getstate(), words and index (624 included)
             syncs += 1
             if syncs == 3:
                 stop = t + 60                            # keep stepping past the last sync
@@ -1042,8 +956,7 @@ def test_greedy_policy_and_clear_heavy_parity():
     G = _engine()
     n, T, W, H = 128, 240, 10, 20
     seeds = [21 + e for e in range(n)]
-    kw = dict(width=W, height=H, advanced_clears=True, penalise_holes_increase=True,
-              penalise_height_increase=True)
+    kw = dict(width=W, height=H, **C4)
     b = G.TetrisBatch(n, autoreset="same_step", seeds=seeds, **kw)
     b.reset()
     acts = np.zeros((T, n), np.uint8)
@@ -1056,18 +969,14 @@ def test_greedy_policy_and_clear_heavy_parity():
                 assert int(a0[e]) == _greedy_ref(st["board"][:, e], W, H, int(st["piece"][e])), (t, e)
         a = b.policy_greedy(t, seed=3, explore=30)
         acts[t] = a.cpu().numpy()
-        o, r, d = b.step(a)
-        got.append((o.cpu().numpy().view(np.uint32).T.copy(), r.cpu().numpy().copy(),
-                    d.cpu().numpy().astype(np.uint8)))
+        got.append(tuple(x.clone() for x in b.step(a)))
     ob = O.OracleBatch(n, seeds, **kw)
     ob.reset()
     ref = ob.rollout(acts)
     # st_step on the clear-heavy trajectory (its line clears with the preview
     # and draw wave live; get_state above syncs only every 40 steps)
     for t in range(T):
-        assert np.array_equal(got[t][1], ref["reward"][t]), t
-        assert np.array_equal(got[t][2], ref["done"][t]), t
-        assert np.array_equal(got[t][0], ref["obs"][t]), t
+        check_step(ref, t, *got[t])
     c = G.TetrisBatch(n, autoreset="same_step", seeds=seeds, **kw)
     c.reset()
     obs, rew, done = c.rollout(torch.as_tensor(acts, device=c.device))
@@ -1147,10 +1056,7 @@ def test_wrapper_validation():
             b.step(torch.as_tensor(bad, device=b.device))
     with pytest.raises(TypeError):
         b.step(torch.zeros(10, dtype=torch.complex64, device=b.device))
-    before = b.get_state()
-    after = b.get_state()
-    for k in before:  # rejected calls did not step
-        assert np.array_equal(before[k], after[k])
+    assert_same_state(b, b)  # (two reads of the state agree; nothing of the above stepped)
     b.step(torch.arange(10, device=b.device) % 7)     # int64 device actions in range
     b.step(np.full(10, 2.0))                         # integral floats in range
     b.step(torch.full((10,), 3.0, device=b.device))
@@ -1194,9 +1100,7 @@ def test_save_load_snapshot(tmp_path):
         for t in range(K):
             o = eng.step(eng.gen_actions(40 + t, 9))
             assert all(torch.equal(x, y) for x, y in zip(o, outs[t])), t
-        st = eng.get_state()
-        for k in fin:
-            assert np.array_equal(st[k], fin[k]), k
+        assert_same_state(fin, eng)
     c = G.TetrisBatch(n + 1, seeds=list(range(n + 1)))
     with pytest.raises(StError):
         c.load(snap)                       # other env count
@@ -1235,9 +1139,7 @@ def test_host_written_lock_fields(lock_delay, step_reset):
     ro, rr, rd = b.rollout(torch.as_tensor(acts, device=b.device))
     for t in range(T):
         o, r, d = a.step(torch.as_tensor(acts[t], device=a.device), obs="packed")
-        assert np.array_equal(r.cpu().numpy(), ref["reward"][t]), t
-        assert np.array_equal(d.cpu().numpy().astype(np.uint8), ref["done"][t]), t
-        assert np.array_equal(o.cpu().numpy().view(np.uint32).T, ref["obs"][t]), t
+        check_step(ref, t, o, r, d)
         assert torch.equal(ro[t], o) and torch.equal(rr[t], r) and torch.equal(rd[t], d), t
 
 
@@ -1251,12 +1153,8 @@ def test_host_written_large_shape_counts(mode):
     a mix.  The first wave's counts spread 14..17 apart (the boundary of
     round 5's measured-and-dropped draw word).  Outputs
     and final counts / MT index vs the oracle."""
-    G = _engine()
     n, T = 256, 80
-    b = G.TetrisBatch(n, autoreset="same_step", seeds=range(n))
-    b.reset()
-    ob = O.OracleBatch(n, list(range(n)))
-    ob.reset()
+    b, ob = batch_and_oracle(n, range(n))
     st = b.get_state(("mt", "stats"))  # st_mt_sync: no preview drawn with the old counts
     mt, stats = st["mt"].copy(), st["stats"].copy()
     rng = np.random.default_rng(23)
@@ -1270,25 +1168,17 @@ def test_host_written_large_shape_counts(mode):
         else:
             counts = stats[6:13, i].astype(np.int64)
         stats[6:13, i] = counts
-        e = ob.envs[i]
-        for k in range(624):
-            e.rng.mt[k] = int(mt[i, k])
-        e.rng.index = int(stats[13, i])
         ob.set_state(i, counts=counts)
+    set_mt_state(ob, mt, stats[13])
     b.set_state(mt=mt, stats=stats)
     acts = O.splitmix64_actions(9, 0, T, n)
     acts[1::2] = 2  # hard drops: a lock at least every other step
     ref = ob.rollout(acts)
     if mode == "step":
         for t in range(T):
-            obs, rew, done = b.step(torch.as_tensor(acts[t], device=b.device))
-            assert np.array_equal(rew.cpu().numpy(), ref["reward"][t]), t
-            assert np.array_equal(obs.cpu().numpy().view(np.uint32).T, ref["obs"][t]), t
+            check_step(ref, t, *b.step(torch.as_tensor(acts[t], device=b.device)))
     else:
-        obs, rew, done = b.rollout(torch.as_tensor(acts, device=b.device))
-        assert np.array_equal(rew.cpu().numpy(), ref["reward"])
-        assert np.array_equal(done.cpu().numpy().astype(np.uint8), ref["done"])
-        assert np.array_equal(obs.cpu().numpy().view(np.uint32).transpose(0, 2, 1), ref["obs"])
+        check_steps(ref, *b.rollout(torch.as_tensor(acts, device=b.device)))
     fin = b.get_state(("mt", "stats"))
     for i in range(n):
         assert list(fin["stats"][6:13, i].astype(np.int64)) == list(np.ctypeslib.as_array(ob.envs[i].counts)), i
@@ -1327,9 +1217,7 @@ def test_step_n_equals_k_step_calls():
             assert torch.equal(f, ob)
             ob = b.obs
         assert torch.equal(o, ob) and torch.equal(r, rb) and torch.equal(d.bool(), db.bool())
-        sa, sb = a.get_state(("board", "stats", "mt")), b.get_state(("board", "stats", "mt"))
-        for key in sa:
-            assert np.array_equal(sa[key], sb[key]), (key, f32)
+        assert_same_state(a, b, f32, ("board", "stats", "mt"))
         a.close()
         b.close()
 
@@ -1352,17 +1240,12 @@ def test_engine_step_n_equals_step_calls(obs):
     torch.cuda.synchronize()
     assert (oa is None) == (ob is None) and (oa is None or torch.equal(oa, ob))
     assert torch.equal(ra, rb) and torch.equal(da, db)
-    sa, sb = a.get_state(("board", "stats", "mt")), b.get_state(("board", "stats", "mt"))
-    for key in sa:
-        assert np.array_equal(sa[key], sb[key]), key
+    assert_same_state(a, b, fields=("board", "stats", "mt"))
     bad = acts.clone()
     bad[3, 7] = 9
-    before = a.get_state(("board", "stats", "mt"))
-    before = {key: v.copy() for key, v in before.items()}
+    before = engine_state(a, ("board", "stats", "mt"))
     with pytest.raises(KeyError):
         a.step_n(bad, obs=obs)
-    after = a.get_state(("board", "stats", "mt"))
-    for key in before:
-        assert np.array_equal(before[key], after[key]), key
+    assert_same_state(before, a, fields=("board", "stats", "mt"))
     a.close()
     b.close()

@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_parity import _engine
+from harness import assert_same_state, engine as _engine, engine_state
 
 pytestmark = pytest.mark.gpu
 
@@ -32,9 +32,7 @@ def _delay(ms_target: float = 30.0):
         x = x @ x
 
 
-def _state(b):
-    st = b.get_state(("board", "stats", "mt"))
-    return {k: v.copy() for k, v in st.items()}
+FIELDS = ("board", "stats", "mt")
 
 
 @pytest.mark.parametrize("obs", ["packed", "f32"])
@@ -56,7 +54,7 @@ def test_gate_rejects_before_any_state_change(obs):
         ob, rb, db = step(b, acts)
         assert torch.equal(oa, ob) and torch.equal(ra, rb) and torch.equal(da, db), t
         if t in (10, 25):
-            before = _state(a)
+            before = engine_state(a, FIELDS)
             good = b.gen_actions(100 + t, 3)
             bads = [good.clone(), good.to(torch.int64), good.to(torch.int64), good.to(torch.float32),
                     good.to(torch.float32)]
@@ -68,9 +66,7 @@ def test_gate_rejects_before_any_state_change(obs):
             for x in bads:
                 with pytest.raises(KeyError):
                     step(a, x)
-            after = _state(a)
-            for k in before:
-                assert np.array_equal(before[k], after[k]), (k, t)
+            assert_same_state(before, a, t, FIELDS)
     # in-range non-uint8 device actions pass the gate
     oa, ra, da = step(a, torch.arange(n, device=a.device) % 7)
     ob, rb, db = step(b, torch.arange(n, device=b.device) % 7)
@@ -106,9 +102,7 @@ def test_gate_ends_at_wait_even_without_its_step():
     ob, rb, db = b.step(good)
     torch.cuda.synchronize()
     assert torch.equal(o, ob) and torch.equal(r, rb) and torch.equal(d.bool(), db.bool())
-    sa, sb = _state(a), _state(b)
-    for k in sa:
-        assert np.array_equal(sa[k], sb[k]), k
+    assert_same_state(a, b, fields=FIELDS)
     a.close()
     b.close()
 

@@ -18,34 +18,12 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_long_horizon import ASEED, SEED_BASE, ParallelOracle
-from test_gpu_parity import _engine
+from harness import (ASEED, C4, SEED_BASE, ParallelOracle, check_final_observation, check_info, check_step,
+                     engine as _engine, unpack_f32, words)
 
 pytestmark = pytest.mark.gpu
 
 W, H = 10, 20
-
-
-C4 = dict(advanced_clears=True, penalise_holes_increase=True, penalise_height_increase=True)
-
-
-def _unpack_f32(words, h=H):
-    """packed obs [n][W] u32 -> float32 [n][W][h]."""
-    return ((words[:, :, None] >> np.arange(h, dtype=np.uint32)) & 1).astype(np.float32)
-
-
-def _check_info(info, ref_st, done, t):
-    st = ref_st  # [n][8]: time, score, lines, holes, deaths, piece id, height, lock (before the reset)
-    zero = np.zeros_like(st[:, 0])
-    want = {"time": np.where(done, zero, st[:, 0]), "score": np.where(done, zero, st[:, 1]),
-            "lines_cleared": np.where(done, zero, st[:, 2]), "holes": np.where(done, zero, st[:, 3]),
-            "deaths": st[:, 4], "piece_height": np.where(done, zero, st[:, 6]),
-            "ep_time": np.where(done, st[:, 0], zero), "ep_score": np.where(done, st[:, 1], zero),
-            "ep_lines": np.where(done, st[:, 2], zero), "ep_holes": np.where(done, st[:, 3], zero)}
-    for k, v in want.items():
-        assert np.array_equal(info[k].cpu().numpy(), v), (k, t)
-    cp = info["current_piece"].cpu().numpy()
-    assert np.array_equal(cp[~done], st[~done, 5]), ("current_piece", t)
 
 
 @pytest.mark.timeout(300)
@@ -62,7 +40,7 @@ def test_vec_env_conventions_vs_oracle(n, w, h, kw):
     b = G.TetrisVecEnv(n, width=w, height=h, seed=SEED_BASE, obs_format="packed", autoreset_obs="terminal", **kw)
     a.reset()
     b.reset()
-    orc = ParallelOracle(n, dict(kw, width=w, height=h))
+    orc = ParallelOracle(n, kw, board=(w, h))
     acts = torch.empty(n, dtype=torch.uint8, device=a.device)
     CH = 50
     ndone = 0
@@ -76,20 +54,13 @@ def test_vec_env_conventions_vs_oracle(n, w, h, kw):
                 ob, rb, db, ib = b.step(acts)
                 done = ref["done"][i].astype(bool)
                 robs = ref["obs"][i]  # [n][W] terminal obs where done
-                for r_, d_ in ((ra, da), (rb, db)):
-                    assert np.array_equal(r_.cpu().numpy(), ref["reward"][i]), ("reward", t)
-                    assert np.array_equal(d_.cpu().numpy(), done), ("done", t)
-                got_a = oa.cpu().numpy().view(np.uint32).T
-                want_a = np.where(done[:, None], 0, robs)
-                assert np.array_equal(got_a, want_a), ("reset-convention obs", t)
-                assert np.array_equal(ob.cpu().numpy().view(np.uint32).T, robs), ("terminal obs", t)
-                assert np.array_equal(ia["_final_observation"].cpu().numpy(), done), t
-                fin = ia["final_observation"].cpu().numpy().view(np.uint32).T
-                assert np.array_equal(fin, np.where(done[:, None], robs, 0)), ("final_observation", t)
+                check_step(ref, i, oa, ra, da, np.where(done[:, None], 0, robs), at=t)  # the reset convention
+                check_step(ref, i, ob, rb, db, at=t)  # the terminal obs
+                check_final_observation(ia, robs, done, t)
                 assert "final_observation" not in ib
-                _check_info(ia, ref["stats"][i], done, t)
+                check_info(ia, ref["stats"][i], done, t)
                 if i % 10 == 0:
-                    _check_info(ib, ref["stats"][i], done, t)
+                    check_info(ib, ref["stats"][i], done, t)
                 ndone += int(done.sum())
         fin_state = orc.final_state()
         for info in (ia, ib):
@@ -130,8 +101,8 @@ def test_vec_env_f32_and_image_conventions(obs_type, n, w, h, kw):
         ret = torch.where(dp.unsqueeze(0), empty, op)
         fin = torch.where(dp.unsqueeze(0), op, empty)
         if obs_type == "ram":
-            want = torch.from_numpy(_unpack_f32(ret.cpu().numpy().view(np.uint32).T, h)).to(a.device)
-            wfin = torch.from_numpy(_unpack_f32(fin.cpu().numpy().view(np.uint32).T, h)).to(a.device)
+            want = torch.from_numpy(unpack_f32(words(ret), h)).to(a.device)
+            wfin = torch.from_numpy(unpack_f32(words(fin), h)).to(a.device)
         else:
             want = p.engine.grayscale(ret, 84, 1).squeeze(-1)
             wfin = p.engine.grayscale(fin, 84, 1).squeeze(-1)

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from harness import C4, assert_same_state, batch_and_oracle, check_step
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -43,7 +44,7 @@ def pack_np(obs, rew, done, W, H):
 
 @pytest.mark.parametrize("W,H,n,kw", [
     (10, 20, 1000, dict()),
-    (10, 20, 777, dict(advanced_clears=True, penalise_holes_increase=True, penalise_height_increase=True)),
+    (10, 20, 777, C4),
     (10, 20, 513, dict(high_scoring=True, reward_step=True, penalise_holes=True, penalise_height=True)),
     (6, 9, 300, dict(penalise_holes=True, penalise_height=True, lock_delay=1, step_reset=True)),
     (32, 28, 130, dict(high_scoring=True)),
@@ -75,29 +76,20 @@ def test_step_wire_equals_step(W, H, n, kw):
         deaths += int(sd.sum())
         neg += int((sr < 0).sum())
     assert deaths > 0 and neg > 0
-    sa, sb = a.get_state(), b.get_state()
-    for k in sa:
-        assert np.array_equal(sa[k], sb[k]), k
+    assert_same_state(a, b)
 
 
 def test_step_wire_full_size_vs_oracle():
     """65,536 envs (C3), 60 steps: unwire(step_wire) == the C oracle."""
-    import gym_simpletetris_amd as G
     from gym_simpletetris_amd.engine import unwire
     n, steps = 65536, 60
-    b = G.TetrisBatch(n, autoreset="same_step", seeds=[9 + e for e in range(n)])
-    b.reset()
-    ob = O.OracleBatch(n, [9 + e for e in range(n)], width=10, height=20)  # rollout auto-resets on done
-    ob.reset()
+    b, ob = batch_and_oracle(n, [9 + e for e in range(n)])  # (the oracle's rollout auto-resets on done)
     acts = O.splitmix64_actions(21, 0, steps, n)
     ref = ob.rollout(acts)
     out = torch.empty((b.wire_words, n), dtype=torch.int32, device=b.device)
     for t in range(steps):
         b.step_wire(torch.as_tensor(acts[t], device=b.device), out=out)
-        o, r, d = unwire(out, 10, 20)
-        assert np.array_equal(r.cpu().numpy(), ref["reward"][t]), t
-        assert np.array_equal(d.cpu().numpy().astype(np.uint8), ref["done"][t]), t
-        assert np.array_equal(o.cpu().numpy().view(np.uint32).T, ref["obs"][t]), t
+        check_step(ref, t, *unwire(out, 10, 20))
 
 
 def test_step_wire_large_rewards_vs_oracle():
@@ -135,9 +127,7 @@ def test_step_wire_large_rewards_vs_oracle():
         so, sr, sd = a.step(act, obs="packed")
         uo, ur, ud = unwire(b.step_wire(act), 10, 20)
         assert torch.equal(uo, so) and torch.equal(ur, sr) and torch.equal(ud, sd), t
-        assert np.array_equal(ur.cpu().numpy(), ref["reward"][t]), t
-        assert np.array_equal(ud.cpu().numpy().astype(np.uint8), ref["done"][t]), t
-        assert np.array_equal(uo.cpu().numpy().view(np.uint32).T, ref["obs"][t]), t
+        check_step(ref, t, uo, ur, ud)
         big += int((ur.abs() >= 1 << 15).sum())
     assert big >= n // 2, big  # every env's first lock: |reward| > 2^15
 
