@@ -359,6 +359,25 @@ int st_export_env(st_ctx *c, int64_t env, const uint32_t *d_obs, const int32_t *
     return ST_OK;
 }
 
+int st_step_export(st_ctx *c, const uint8_t *d_actions, int64_t env, uint32_t parts, uint32_t *d_out,
+                   uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream) {
+    if (!c || !d_actions || !d_out || !d_obs || !d_reward || !d_done)
+        return fail(ST_EINVAL, "st_step_export: null argument");
+    if (env < 0 || env >= c->n) return fail(ST_EINVAL, "st_step_export: env %lld of %lld", (long long)env,
+                                            (long long)c->n);
+    if (parts & ~(ST_EXPORT_MT | ST_EXPORT_OBS_F32)) return fail(ST_EINVAL, "st_step_export: parts 0x%x", parts);
+    if (!c->seeded || !c->reset_once)
+        return fail(ST_ESTATE, "st_step_export before st_seed + st_reset (tetris_env.py:244 needs an anchor)");
+    DeviceGuard g(c->device);
+    st::KParams p = params(c);  // (not gated: an armed st_gate_actions stays armed)
+    p.actions = d_actions;
+    p.obs = d_obs;
+    p.reward = d_reward;
+    p.done = d_done;
+    ST_HIP(st::launch_step_export(p, env, parts, d_out, (hipStream_t)stream));
+    return ST_OK;
+}
+
 int st_export_words(int32_t width, int32_t height) {
     return width + 2 + ST_NSTAT + st::kMtN + width * height;
 }

@@ -16,6 +16,14 @@
 // The column words carry "floor" bits at rows >= H and the kPad columns on
 // each side are all-ones walls, so a collision test is four AND-tests with no
 // bounds checks and hard_drop is a count-trailing-zeros per piece column.
+//
+// Two translation units are built from this file: the library's kernels (as it
+// is) and, with ST_STEP_EXPORT_TU defined (st_step_export.hip), k_step_export
+// and its launcher alone.  step_logic / step_draw are shared source, but a
+// second kernel instantiating them in ONE module changes the code the
+// compiler emits for k_step itself (it did: four instructions around the lock
+// ballot's LDS read); in a module of its own the new kernel cannot touch the
+// code objects of k_step, k_rollout and k_rollout2.
 #include "st_internal.h"
 
 
@@ -3117,6 +3125,7 @@ constexpr uint32_t kScoringFlags =
     ST_PENALISE_HEIGHT | ST_PENALISE_HEIGHT_INCREASE | ST_ADVANCED_CLEARS | ST_HIGH_SCORING |
     ST_PENALISE_HOLES | ST_PENALISE_HOLES_INCREASE;
 
+#ifndef ST_STEP_EXPORT_TU
 // ---------------------------------------------------------------- reset
 // TetrisEngine.clear (tetris_env.py:306-315) on masked envs.  n_deaths,
 // shape_counts and the lock-delay counter persist (R15).
@@ -3296,6 +3305,7 @@ __global__ __launch_bounds__(kWave) void k_render(KParams p) {
     if (e < p.n)
         for (int x = 0; x < W; ++x) p.obs[x * p.n + e] = lcol(L, x, lane) & hmask;
 }
+#endif  // !ST_STEP_EXPORT_TU
 
 // ---------------------------------------------------------------- export
 // st_export_env: one env's outputs and state as one record (the single-env
@@ -3306,12 +3316,20 @@ __global__ __launch_bounds__(kWave) void k_render(KParams p) {
 // position): the env keeps its preview and next-generation progress.  The
 // float32 obs saves the host the bit unpacking (the record is written
 // straight into mapped pinned memory).
-__global__ __launch_bounds__(256) void k_export(KParams p, int64_t env, const uint32_t *obs,
-                                               const int32_t *rew, const uint8_t *done, uint32_t parts,
-                                               uint32_t *out) {
+// One writer for both launches that produce it (k_export and k_step_export's
+// tail): thread `tid` of `nthreads` cooperating threads.  Its loads are
+// non-temporal (served by L2, past the CU's L1): in k_step_export they read
+// what other waves of the workgroup stored in the same launch.
+template <typename T>
+__device__ __forceinline__ T ld_l2(const T *p) {
+    return __builtin_nontemporal_load(p);
+}
+__device__ __forceinline__ void export_record(const KParams &p, int64_t env, const uint32_t *obs, const int32_t *rew,
+                                              const uint8_t *done, uint32_t parts, uint32_t *out, int tid,
+                                              int nthreads) {
     const int W = p.W, H = p.H;
     const int head = W + 2 + ST_NSTAT;
-    const uint32_t r = (uint32_t)p.stats[(int64_t)ST_STAT_MT_INDEX * p.stride + env];
+    const uint32_t r = (uint32_t)ld_l2(&p.stats[(int64_t)ST_STAT_MT_INDEX * p.stride + env]);
     int idx = (int)(r & 0x3FFu);
     uint32_t cur = (r >> 20) & 1u;
     if (pv_ok(r)) {  // see k_mt_sync
@@ -3323,29 +3341,87 @@ __global__ __launch_bounds__(256) void k_export(KParams p, int64_t env, const ui
             cur ^= 1u;
         }
     }
-    for (int i = threadIdx.x; i < head; i += blockDim.x) {
+    for (int i = tid; i < head; i += nthreads) {
         uint32_t v;
-        if (i < W) v = obs ? obs[(int64_t)i * p.n + env] : 0u;
-        else if (i == W) v = rew ? (uint32_t)rew[env] : 0u;
-        else if (i == W + 1) v = done ? (uint32_t)done[env] : 0u;
+        if (i < W) v = obs ? ld_l2(&obs[(int64_t)i * p.n + env]) : 0u;
+        else if (i == W) v = rew ? (uint32_t)ld_l2(&rew[env]) : 0u;
+        else if (i == W + 1) v = done ? (uint32_t)ld_l2(&done[env]) : 0u;
         else if (i == W + 2 + ST_STAT_MT_INDEX) v = (uint32_t)idx;
-        else v = (uint32_t)p.stats[(int64_t)(i - W - 2) * p.stride + env];
+        else v = (uint32_t)ld_l2(&p.stats[(int64_t)(i - W - 2) * p.stride + env]);
         out[i] = v;
     }
     if (parts & ST_EXPORT_MT) {
         const uint32_t *g = p.mt + env * kMtPitch + (cur ? kMtB : 0u);
-        for (int i = threadIdx.x; i < kMtN; i += blockDim.x) out[head + i] = g[i];
+        for (int i = tid; i < kMtN; i += nthreads) out[head + i] = ld_l2(&g[i]);
     }
     if (parts & ST_EXPORT_OBS_F32) {
         float *f = reinterpret_cast<float *>(out + head + kMtN);
-        for (int i = threadIdx.x; i < W * H; i += blockDim.x) {
+        for (int i = tid; i < W * H; i += nthreads) {
             const int x = i / H, y = i - x * H;
-            const uint32_t w = obs ? obs[(int64_t)x * p.n + env] : 0u;
+            const uint32_t w = obs ? ld_l2(&obs[(int64_t)x * p.n + env]) : 0u;
             f[i] = (float)((w >> y) & 1u);
         }
     }
 }
 
+#ifndef ST_STEP_EXPORT_TU
+__global__ __launch_bounds__(256) void k_export(KParams p, int64_t env, const uint32_t *obs,
+                                               const int32_t *rew, const uint8_t *done, uint32_t parts,
+                                               uint32_t *out) {
+    export_record(p, env, obs, rew, done, parts, out, (int)threadIdx.x, (int)blockDim.x);
+}
+
+#else  // ST_STEP_EXPORT_TU
+// st_step_export: k_step (packed outputs, no stamps, not gated) with the
+// export record of one env written by the workgroup that stepped it -- the
+// single-env surface's step and read-back in ONE launch.  Both waves run
+// step_logic / step_draw unchanged and meet at one more workgroup barrier
+// (each has passed B0 and B1 once: neither role returns early without VEC);
+// behind it the workgroup's 128 threads write the record from what the two
+// waves stored to global memory moments before: obs / reward / done and the
+// hot counter rows (logic wave), the count rows, the MT index word, the MT
+// words and the next-generation chunk (draw wave).
+// What orders the tail's loads behind those stores ("The fused
+// tail"): (1) each wave waits for its own stores before it arrives -- an
+// explicit s_waitcnt vmcnt(0), because a workgroup-scope release fence on
+// gfx950 waits for LDS traffic only and s_barrier waits for no counter; a
+// store counted out of vmcnt has been acknowledged by L2, `nt` or not;
+// (2) the workgroup barrier; (3) the tail's loads are issued behind it (the
+// acquire fence keeps the compiler from moving them up), are vector loads
+// (memory the kernel itself stored to is never read through the scalar
+// cache) and non-temporal, i.e. served by L2, where the stores are.  Were
+// they served by the CU's L1 instead, the LLVM AMDGPU memory model's rule for
+// gfx942 / gfx950 would hold: the waves of a workgroup share one
+// write-through L1 (no threadgroup-split mode here), which their stores
+// went through.  Other workgroups skip the wait, the barrier and the tail
+// (the branch is workgroup-uniform): for them this is k_step.
+template <int WT, int HT, bool SC0>
+__global__ __launch_bounds__(2 * kWave) void k_step_export(uint32_t *board, int32_t *stats, const uint8_t *actions,
+                                                           uint32_t *mt, int64_t stride, int64_t n, KParams p0,
+                                                           int64_t env, uint32_t *obs, int32_t *rew, uint8_t *done,
+                                                           uint32_t parts, uint32_t *out) {
+    KParams p = p0;
+    p.board = board;
+    p.stats = stats;
+    p.actions = actions;
+    p.mt = mt;
+    p.stride = stride;
+    p.n = n;
+    p.obs = obs;
+    p.reward = rew;
+    p.done = done;
+    __shared__ StepLds<WT, false, 1> sm;
+    if (threadIdx.x < kWave) step_logic<WT, HT, false, false, 1, SC0, false>(p, sm);
+    else step_draw<WT, HT, false, false, 1, SC0, false>(p, sm);
+    if ((int64_t)blockIdx.x != env / kWave) return;
+    __builtin_amdgcn_s_setprio(0);  // the tail is nobody's critical chain
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have reached L2
+    wg_barrier();
+    export_record(p, env, obs, rew, done, parts, out, (int)threadIdx.x, 2 * kWave);
+}
+#endif  // ST_STEP_EXPORT_TU
+
+#ifndef ST_STEP_EXPORT_TU
 // ---------------------------------------------------------------- misc
 // Image writers: the output of a block of envs is one contiguous region, so
 // lanes walk it in 16-B chunks (lane-consecutive vector stores, one 1-KB
@@ -3805,8 +3881,27 @@ __global__ __launch_bounds__(kWave) void k_policy_greedy(KParams p, uint64_t see
     if ((uint32_t)(h % 1000ull) < explore) a = (uint32_t)((h >> 32) % 7ull);
     if (e < p.n) out[e] = (uint8_t)a;
 }
+#endif  // !ST_STEP_EXPORT_TU
 
 }  // namespace
+
+// k_step's arguments: the preloaded six, then the whole KParams
+#define ST_STEP_ARGS(p) (p).board, (p).stats, (p).actions, (p).mt, (p).stride, (p).n, (p)
+
+#ifdef ST_STEP_EXPORT_TU
+hipError_t launch_step_export(const KParams &p, int64_t env, uint32_t parts, uint32_t *out, hipStream_t s) {
+    const dim3 grid((unsigned)(p.stride / kWave)), block(2 * kWave);  // logic + draw wave
+#define ST_STEP_EXPORT_ARGS ST_STEP_ARGS(p), env, p.obs, p.reward, p.done, parts, out
+    if (p.W == 10 && p.H == 20) {
+        if (!(p.flags & kScoringFlags)) hipLaunchKernelGGL((k_step_export<10, 20, true>), grid, block, 0, s, ST_STEP_EXPORT_ARGS);
+        else hipLaunchKernelGGL((k_step_export<10, 20, false>), grid, block, 0, s, ST_STEP_EXPORT_ARGS);
+    } else {
+        hipLaunchKernelGGL((k_step_export<0, 0, false>), grid, block, 0, s, ST_STEP_EXPORT_ARGS);
+    }
+#undef ST_STEP_EXPORT_ARGS
+    return hipGetLastError();
+}
+#else  // !ST_STEP_EXPORT_TU
 
 hipError_t launch_seed(const KParams &p, hipStream_t s) {
     const int64_t blocks = (p.stride + 255) / 256;
@@ -3819,8 +3914,6 @@ hipError_t launch_reset(const KParams &p, hipStream_t s) {
     return hipGetLastError();
 }
 
-// k_step's arguments: the preloaded six, then the whole KParams
-#define ST_STEP_ARGS(p) (p).board, (p).stats, (p).actions, (p).mt, (p).stride, (p).n, (p)
 hipError_t launch_step(const KParams &p, hipStream_t s) {
     const dim3 grid((unsigned)(p.stride / kWave)), block(2 * kWave);  // logic + draw wave
     const bool f32 = p.obs_f32 != nullptr;
@@ -4028,5 +4121,7 @@ hipError_t launch_export(const KParams &p, int64_t env, const uint32_t *obs, con
     hipLaunchKernelGGL(k_export, dim3(1), dim3(256), 0, s, p, env, obs, rew, done, parts, out);
     return hipGetLastError();
 }
+
+#endif  // !ST_STEP_EXPORT_TU
 
 }  // namespace st

@@ -90,6 +90,7 @@ SIG = {
     "st_load": ([_vp, _vp, _i64], ctypes.c_int),
     "st_export_env": ([_vp, _i64, _vp, _vp, _vp, _u32, _vp, _vp], ctypes.c_int),
     "st_export_words": ([_i32, _i32], ctypes.c_int),
+    "st_step_export": ([_vp, _vp, _i64, _u32, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_check_actions": ([_vp, _i64, _vp, _vp], ctypes.c_int),
     "st_set_action_flag": ([_vp, _vp], ctypes.c_int),
     "st_gate_actions": ([_vp, _vp, _vp], ctypes.c_int),
@@ -129,8 +130,13 @@ def load(path: str = LIB_PATH):
         raise ImportError(f"{path}: libsimpletetris ABI {abi} != {ABI_VERSION} (rebuild it, or set "
                           "ST_AB_OLD_ABI=1 for a diagnostic A/B of an older build)")
     for name, (args, res) in SIG.items():
-        if ab_override and not hasattr(L, name):
-            continue
+        if not hasattr(L, name):
+            if ab_override:
+                continue
+            # an addition that did not change the ABI number (st_step_export):
+            # the library on disk was built before it
+            raise ImportError(f"{path}: no symbol {name} (a stale build of ABI {abi}: rebuild it with "
+                              "`make -C gym-simpletetris_amd/csrc`)")
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res

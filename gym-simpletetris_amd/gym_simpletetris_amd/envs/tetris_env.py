@@ -1,6 +1,8 @@
 """Gym surface of SimpleTetris-v0 on the MI355X engine.
 
-TetrisEnv     -- the reference's single-env class (tetris_env.py:338-467):
+TetrisEnv     -- the reference's single-env class (tetris_env.py:338-467;
+                 its engine class is envs/tetris_engine.py, the plumbing
+                 both share envs/_single.py):
                  same constructor kwargs, spaces, step/reset/render/close,
                  numpy float32 observations, the reference's reward *types*
                  (int / np.int64 / float / np.float64, R18) and info dict.
@@ -20,7 +22,6 @@ from __future__ import annotations
 
 import collections
 import ctypes
-import random
 import sys
 import weakref
 from typing import Optional
@@ -30,12 +31,8 @@ import torch
 
 from .. import _lib as C
 from .. import spaces
-from ..engine import SHAPE_NAMES, TetrisBatch, scalar_action
-
-
-# counter rows of the export record (st_stat)
-_TIME, _SCORE, _LINES, _HOLES, _DEATHS, _HEIGHT, _C0, _PIECE = (
-    C.STAT[k] for k in ("time", "score", "lines", "holes", "deaths", "piece_height", "count0", "piece"))
+from ..engine import TetrisBatch
+from ._single import SingleEnv
 
 
 def _obs_space(obs_type, width, height, extend_dims):
@@ -51,17 +48,6 @@ def _obs_space(obs_type, width, height, extend_dims):
     return spaces.Box(0, 1, shape=shape, dtype=np.float32)
 
 
-def _stream_sync(sp: ctypes.c_void_p):
-    """A synchronize of stream `sp` through libsimpletetris (st_stream_sync:
-    the runtime its kernels use; torch's stream synchronize costs ~3 us more
-    per call)."""
-    fn = C.load().st_stream_sync
-
-    def sync():
-        C.check(fn(sp))
-    return sync
-
-
 class TetrisEnv:
     metadata = {"render.modes": ["human", "rgb_array"], "render_fps": 8}  # :339
 
@@ -70,196 +56,36 @@ class TetrisEnv:
                  penalise_height_increase=False, advanced_clears=False, high_scoring=False,
                  penalise_holes=False, penalise_holes_increase=False, lock_delay=0,
                  step_reset=False, *, device=None, rng: str = "global", seed: Optional[int] = None):
-        if rng not in ("global", "private"):
-            raise ValueError("rng must be 'global' (CPython's random, like the reference) or 'private'")
         self.width = width
         self.height = height
         self.obs_type = obs_type
         self.extend_dims = extend_dims
         self.render_mode = render_mode
         self.window_size = 512
-        self.engine = TetrisBatch(1, width=width, height=height, lock_delay=lock_delay,
-                                  step_reset=step_reset, reward_step=reward_step,
-                                  penalise_height=penalise_height,
-                                  penalise_height_increase=penalise_height_increase,
-                                  advanced_clears=advanced_clears, high_scoring=high_scoring,
-                                  penalise_holes=penalise_holes,
-                                  penalise_holes_increase=penalise_holes_increase,
-                                  autoreset="none", device=device,
-                                  validate_actions=False)  # step() checks the action itself
-        self._rng_mode = rng
-        self.engine.seed([0 if seed is None else seed])
-        if rng == "global" and seed is not None:
-            random.seed(seed)
-        self._scoring = dict(advanced_clears=advanced_clears, penalise_height=penalise_height,
-                             penalise_height_increase=penalise_height_increase)
+        # the env itself -- record, RNG mirror, live statistics, reward types:
+        # shared with TetrisEngine (envs/_single.py); a step is ONE launch
+        # (st_step_export) and one synchronize, plus the image launch for
+        # grayscale / rgb
+        self._core = SingleEnv(width, height, dict(
+            lock_delay=lock_delay, step_reset=step_reset, reward_step=reward_step,
+            penalise_height=penalise_height, penalise_height_increase=penalise_height_increase,
+            advanced_clears=advanced_clears, high_scoring=high_scoring, penalise_holes=penalise_holes,
+            penalise_holes_increase=penalise_holes_increase), device=device, rng=rng, seed=seed,
+            f32=obs_type == "ram", image_channels={"grayscale": 1, "rgb": 3}.get(obs_type, 0))
+        self.engine = self._core.batch  # the one-env TetrisBatch
         self.action_space = spaces.Discrete(7)           # :377
         self.observation_space = _obs_space(obs_type, width, height, extend_dims)
         self.window = None
         self.clock = None
-        self._stats = None         # last downloaded counters (host int64 [NSTAT])
-        # info['statistics'] is ONE dict for the env's lifetime, updated in
-        # place, like the reference's live shape_counts (tetris_env.py:181,
-        # :199, :240): a held info sees later spawns, and counts written into
-        # it weight the next draws (:183-191)
-        self._shape_counts = None
-        self._shape_vals = None    # what the env last wrote into it
         self._started = False
-        self._rng_sync_state = None
-        dev = self.engine.device
-        L = self.engine._L
-        # per-step plumbing without per-call allocations: one device tensor per
-        # action value, the step's outputs, and ONE read-back record
-        # (st_export_env: obs words | reward | done | counters | MT words in
-        # 'global' mode | float32 obs for 'ram') plus the image for grayscale /
-        # rgb, copied into pinned host buffers and waited for once
-        self._acts = [torch.full((1,), a, dtype=torch.uint8, device=dev) for a in range(7)]
-        self._p_acts = [ctypes.c_void_p(t.data_ptr()) for t in self._acts]
-        self._nrec = int(L.st_export_words(width, height))
-        self._parts = (C.EXPORT_MT if rng == "global" else 0) | (C.EXPORT_OBS_F32 if obs_type == "ram" else 0)
-        self._f32_at = width + 2 + C.NSTAT + C.MT_N  # the record's float32 obs
-        # the export and image kernels write straight into the pinned buffers
-        # when the runtime maps them for the device (else: device buffer + copy)
-        self._rec = self.engine._pinned(self._nrec, torch.int32)
-        self._h_rec_np = self._rec.host.numpy()
-        self._zeros = torch.zeros((width, 1), dtype=torch.int32, device=dev)
-        self._ch = 1 if obs_type == "grayscale" else 3
-        self._img = self.engine._pinned((1, 84, 84, self._ch), torch.float32) \
-            if obs_type in ("grayscale", "rgb") else None
-        self._h_mt = np.zeros(C.MT_N, np.uint32)
-        self._h_idx = np.zeros(1, np.int32)
-        # per-step constants: output pointers, the stream current at
-        # construction (the env issues all its work there), a direct
-        # hipStreamSynchronize (torch's costs ~3 us more per call)
-        self._po, self._pr, self._pd = (ctypes.c_void_p(t.data_ptr())
-                                        for t in (self.engine.obs, self.engine.reward, self.engine.done))
-        self._pz = ctypes.c_void_p(self._zeros.data_ptr())
-        self._sp = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        self._sync = _stream_sync(self._sp)
 
-    # ------------------------------------------------------------- RNG mirror
     def seed(self, seed=None):
         """Seed the piece RNG: random.seed(seed) in 'global' mode (what a user
         of the reference does), the env's private MT19937 otherwise."""
-        if self._rng_mode == "global":
-            random.seed(seed)
-        else:
-            self.engine.seed([0 if seed is None else seed])
+        self._core.seed(seed)
         return [seed]
 
-    def _stream(self):
-        return self._sp
-
-    def _push_rng(self):
-        if self._rng_mode != "global":
-            return
-        state = random.getstate()
-        if self._rng_sync_state is not None and state == self._rng_sync_state:
-            return
-        internal = state[1]
-        self._h_mt[:] = np.asarray(internal[:C.MT_N], dtype=np.uint32)
-        self._h_idx[0] = internal[C.MT_N]
-        eng = self.engine
-        L = eng._L
-        s = self._stream()
-        C.check(L.st_copy(ctypes.c_void_p(eng._view_ptr("mt")), ctypes.c_void_p(self._h_mt.ctypes.data),
-                          C.MT_N * 4, s))
-        C.check(L.st_copy(eng._stat_ptr(C.STAT["mt_index"]), ctypes.c_void_p(self._h_idx.ctypes.data), 4, s))
-        self._rng_sync_state = state  # the device now mirrors CPython's state
-
-    def _readback(self, obs_ptr, rew_ptr, done_ptr, prev_idx=None):
-        """One read-back per call: the env's record (st_export_env: outputs,
-        counters, CPython's form of its MT state in 'global' mode and the
-        float32 obs for 'ram') and, for image observations, its image, each
-        written to pinned host memory on the stream, then ONE synchronize.
-        In 'global' mode CPython's random takes the env's MT state if this
-        call drew pieces.  Returns (float32 obs [W, H] for 'ram' else None,
-        reward, done, counters [NSTAT] as Python ints, image or None)."""
-        eng = self.engine
-        L, ctx = eng._L, eng._ctx
-        s = self._stream()
-        rec, img = self._rec, self._img
-        C.check(L.st_export_env(ctx, 0, obs_ptr, rew_ptr, done_ptr, self._parts, rec.dst, s))
-        if rec.staged:
-            rec.land(s)
-        if img is not None:
-            src = obs_ptr if obs_ptr is not None else self._pz
-            C.check(L.st_grayscale(ctx, src, 84, self._ch, 0, img.dst, s))
-            if img.staged:
-                img.land(s)
-        self._sync()
-        rec = self._h_rec_np
-        W = self.width
-        obs = None
-        if self.obs_type == "ram":  # decoded on the device; a fresh array per step, like np.array(state)
-            a = self._f32_at
-            obs = rec[a:a + W * self.height].view(np.float32).reshape(W, self.height).copy()
-        st = rec[W + 2: W + 2 + C.NSTAT].tolist()  # Python ints (the reference's counters are ints)
-        if self._rng_mode == "global":
-            idx = st[C.STAT["mt_index"]]
-            # the cached state is CPython's current one (_push_rng checked it
-            # before the step); only a step that drew changes it
-            if prev_idx is None or idx != prev_idx or self._rng_sync_state is None:
-                mt = rec[W + 2 + C.NSTAT:W + 2 + C.NSTAT + C.MT_N].view(np.uint32)
-                old = self._rng_sync_state if self._rng_sync_state is not None else random.getstate()
-                new = (old[0], tuple(mt.tolist()) + (idx,), old[2])
-                random.setstate(new)
-                self._rng_sync_state = new
-        if img is not None:
-            img = img.host.numpy()[0].copy()
-        return obs, int(rec[W]), bool(rec[W + 1]), st, img
-
     # ------------------------------------------------------------- gym API
-    def _get_info(self, st):
-        """TetrisEngine.get_info (tetris_env.py:232-241); `st` holds Python
-        ints (the record's counter rows, .tolist()).  'statistics' is the
-        env's one shape-count dict, refreshed in place (the reference returns
-        its live shape_counts, :240)."""
-        vals = tuple(st[_C0:_C0 + 7])
-        d = self._shape_counts
-        if d is None:
-            d = self._shape_counts = dict(zip(SHAPE_NAMES, vals))
-        elif vals != self._shape_vals:
-            for k, v in zip(SHAPE_NAMES, vals):
-                d[k] = v
-        self._shape_vals = vals
-        return {"time": st[_TIME],
-                "current_piece": SHAPE_NAMES[st[_PIECE] & 7],
-                "score": st[_SCORE],
-                "lines_cleared": st[_LINES],
-                "holes": st[_HOLES],
-                "deaths": st[_DEATHS],
-                "statistics": d}
-
-    def _push_counts(self):
-        """Counts the caller wrote into info['statistics'] since the last call
-        take effect like writes into the reference's shape_counts: the next
-        draw (:183-191) sees them, and spawns count on from them (:199).  The
-        device drops its preview (st_mt_sync: the piece drawn one spawn ahead
-        with the old counts) and takes the new counts."""
-        d = self._shape_counts
-        if d is None:
-            return
-        if len(d) == 7 and all(type(d.get(k)) is int for k in SHAPE_NAMES):
-            vals = tuple(d[k] for k in SHAPE_NAMES)
-            if vals == self._shape_vals:
-                return
-        else:
-            vals = None
-        if vals is None or not all(-(1 << 31) <= v < (1 << 31) for v in vals):
-            raise ValueError("info['statistics'] may only hold int32 counts for the keys "
-                             f"{SHAPE_NAMES} (got {dict(d)!r})")
-        eng = self.engine
-        L, s = eng._L, self._stream()
-        C.check(L.st_mt_sync(eng._ctx, s))
-        cnt = np.asarray(vals, dtype=np.int32)
-        for i in range(7):
-            C.check(L.st_copy(eng._stat_ptr(_C0 + i), ctypes.c_void_p(cnt.ctypes.data + 4 * i), 4, s))
-        self._sync()  # (cnt is pageable host memory)
-        self._shape_vals = vals
-        if self._stats is not None:
-            self._stats[_C0:_C0 + 7] = list(vals)  # the reward-type test compares with these
-
     def _observation(self, obs, img):
         """TetrisEnv._observation (tetris_env.py:413-433) + float32 cast, from
         the read-back's float32 obs (ram) or image (grayscale / rgb)."""
@@ -269,50 +95,26 @@ class TetrisEnv:
             return img if self.extend_dims else img.reshape(84, 84)
         return img
 
-    def _typed_reward(self, r: int, done: bool, prev, st):
-        """Reproduce the Python type the reference's reward ends up with (R18)."""
-        if done:
-            return int(r)
-        if st[_C0:_C0 + 7] == prev[_C0:_C0 + 7]:  # no new piece: the step did not lock
-            return int(r)
-        if self._scoring["advanced_clears"]:
-            hp = _HEIGHT
-            if self._scoring["penalise_height"] or (
-                    self._scoring["penalise_height_increase"] and st[hp] > prev[hp]):
-                return np.float64(r)
-            return float(r)
-        return np.int64(r)
-
     def step(self, action):
         """TetrisEnv.step (tetris_env.py:397-403)."""
         if not self._started:
             raise AttributeError("step() before reset(): the reference fails at tetris_env.py:244")
-        action = scalar_action(action)  # value_action_map[action]'s KeyError, tetris_env.py:245
-        self._push_counts()
-        prev = self._stats
-        self._push_rng()
-        eng = self.engine
-        C.check(eng._L.st_step(eng._ctx, self._p_acts[action], self._po, self._pr, self._pd, self._sp))
-        obs, r, d, st, img = self._readback(self._po, self._pr, self._pd, prev[C.STAT["mt_index"]])
-        self._stats = st
-        return self._observation(obs, img), self._typed_reward(r, d, prev, st), d, self._get_info(st)
+        core = self._core
+        obs, r, d, st, img = core.step(action)
+        return self._observation(obs, img), r, d, core.info(st)
 
     def reset(self, return_info=False):
         """TetrisEnv.reset (tetris_env.py:405-411): clear(); obs is the empty
         board (clear() returns the board before the new piece is drawn)."""
-        self._push_counts()
-        self._push_rng()
-        C.check(self.engine._L.st_reset(self.engine._ctx, None, self._sp))  # clear() on the env's stream
+        obs, st, img = self._core.reset()
         self._started = True
-        obs, _, _, st, img = self._readback(self._pz, None, None)
-        self._stats = st
         obs = self._observation(obs, img)
-        return (obs, self._get_info(st)) if return_info else obs
+        return (obs, self._core.info(st)) if return_info else obs
 
     def render(self, mode="human"):
         """render('rgb_array'): 160x160x3 uint8 frame (tetris_env.py:458-462)."""
         if mode == "rgb_array":
-            self._sync()  # the env's own stream first (its steps), then the current one
+            self._core.sync()  # the env's own stream first (its steps), then the current one
             packed = self.engine.render_packed()
             img = self.engine.grayscale(packed, 160, 3, as_u8=True)[0]
             return img.cpu().numpy()
@@ -323,7 +125,7 @@ class TetrisEnv:
     def close(self):
         """tetris_env.py:466-467."""
         if getattr(self, "engine", None) is not None:
-            self.engine.close()
+            self._core.close()
             self.engine = None
 
 

@@ -34,6 +34,8 @@ extern "C" {
 /* 2: st_step_wire carries the reward's 32 bits (st_wire_words grew by one
  * word for 10x20), st_unwire_shards.  3: st_gate_actions / st_gate_wait,
  * st_stream_wait (additions only).  4: st_step_n (addition only).
+ * st_step_export: addition only, version unchanged (a build without it is
+ * refused by the host package when it binds the symbol).
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -261,6 +263,18 @@ int st_grayscale(st_ctx *ctx, const uint32_t *d_obs, int32_t size, int32_t chann
 int st_export_env(st_ctx *ctx, int64_t env, const uint32_t *d_obs, const int32_t *d_reward,
                   const uint8_t *d_done, uint32_t parts, uint32_t *d_out, st_stream stream);
 int st_export_words(int32_t width, int32_t height);
+
+/* st_step (d_obs, d_reward, d_done) followed by st_export_env(env, the same
+ * three, parts, d_out), in ONE launch: every env steps (TetrisEngine.step,
+ * tetris_env.py:243-304), env's record is written by the workgroup that
+ * stepped it.  d_obs, d_reward, d_done and d_out are all required (the
+ * record is read back from them; d_out may be mapped pinned host memory, as
+ * for st_export_env).  ST_EINVAL for a NULL, env outside [0, n_envs) or
+ * parts outside the two flags; ST_ESTATE before st_seed + st_reset; all
+ * before any GPU call.  Like st_step_wire it is not gated and does not
+ * consume an armed gate; it honours st_set_action_flag as st_step does. */
+int st_step_export(st_ctx *ctx, const uint8_t *d_actions, int64_t env, uint32_t parts, uint32_t *d_out,
+                   uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
 
 /* Device views of the state (valid until st_destroy). */
 int st_state(st_ctx *ctx, st_state_views *out);
