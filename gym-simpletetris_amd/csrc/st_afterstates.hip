@@ -1,0 +1,9 @@
+// st_afterstates.hip -- k_afterstates (st_afterstates) and k_placement_actions
+// (st_placement_actions) as a translation unit of their own: the kernels and
+// their launchers live in st_kernels.hip beside the piece table and the
+// collision / drop / clear / scoring helpers they share with the step
+// kernels, and are compiled here, apart from them, so that adding them leaves
+// the code objects of k_step / k_rollout / k_rollout2 / k_step_export exactly
+// as they were (st_kernels.hip, top).
+#define ST_AFTERSTATES_TU 1
+#include "st_kernels.hip"

@@ -524,6 +524,28 @@ int st_policy_greedy(st_ctx *c, uint64_t seed, int64_t t, uint32_t explore_permi
     return ST_OK;
 }
 
+int st_after_slots(int32_t width) {
+    if (width < 4 || width > st::kMaxW)
+        return fail(ST_EINVAL, "st_after_slots: width %d outside [4, %d]", width, st::kMaxW);
+    return 4 * (width + 6);
+}
+
+int st_afterstates(st_ctx *c, int32_t *d_feat, uint32_t *d_boards, st_stream stream) {
+    if (!c || !d_feat) return fail(ST_EINVAL, "st_afterstates: null argument");
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_afterstates before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    ST_HIP(st::launch_afterstates(params(c), d_feat, d_boards, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_placement_actions(st_ctx *c, const int32_t *d_slots, uint8_t *d_actions, st_stream stream) {
+    if (!c || !d_slots || !d_actions) return fail(ST_EINVAL, "st_placement_actions: null argument");
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_placement_actions before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    ST_HIP(st::launch_placement_actions(params(c), d_slots, d_actions, (hipStream_t)stream));
+    return ST_OK;
+}
+
 int st_check_actions(const uint8_t *d_actions, int64_t n, uint32_t *d_flag, st_stream stream) {
     if (n < 0) return fail(ST_EINVAL, "st_check_actions: negative size");
     if (n > 0 && (!d_actions || !d_flag)) return fail(ST_EINVAL, "st_check_actions: null argument");

@@ -90,6 +90,9 @@ hipError_t launch_export(const KParams &p, int64_t env, const uint32_t *obs, con
 hipError_t launch_mt_sync(const KParams &p, hipStream_t s);
 hipError_t launch_policy_greedy(const KParams &p, uint64_t seed, int64_t t, uint32_t explore,
                                 uint8_t *out, hipStream_t s);
+// st_afterstates: feat int32 [n][ST_AFTER_NFEAT][S], boards uint32 [n][W][S] or null (S = 4 * (W + 6))
+hipError_t launch_afterstates(const KParams &p, int32_t *feat, uint32_t *boards, hipStream_t s);
+hipError_t launch_placement_actions(const KParams &p, const int32_t *slots, uint8_t *out, hipStream_t s);
 hipError_t launch_grayscale(const KParams &p, const uint32_t *obs, int size, int channels,
                             int as_u8, void *out, hipStream_t s);
 hipError_t launch_unwire(int W, int H, int64_t n_global, int shards, int64_t n_cap, const uint32_t *wire,

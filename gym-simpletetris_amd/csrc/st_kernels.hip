@@ -17,14 +17,20 @@
 // each side are all-ones walls, so a collision test is four AND-tests with no
 // bounds checks and hard_drop is a count-trailing-zeros per piece column.
 //
-// Two translation units are built from this file: the library's kernels (as it
-// is) and, with ST_STEP_EXPORT_TU defined (st_step_export.hip), k_step_export
-// and its launcher alone.  step_logic / step_draw are shared source, but a
-// second kernel instantiating them in ONE module changes the code the
-// compiler emits for k_step itself (it did: four instructions around the lock
-// ballot's LDS read); in a module of its own the new kernel cannot touch the
-// code objects of k_step, k_rollout and k_rollout2.
+// Three translation units are built from this file: the library's kernels (as
+// it is); with ST_STEP_EXPORT_TU defined (st_step_export.hip), k_step_export
+// and its launcher alone; with ST_AFTERSTATES_TU defined (st_afterstates.hip),
+// k_afterstates, k_placement_actions and their launchers alone.  step_logic /
+// step_draw are shared source, but a second kernel instantiating them in ONE
+// module changes the code the compiler emits for k_step itself (it did: four
+// instructions around the lock ballot's LDS read); in a module of its own a
+// new kernel cannot touch the code objects of k_step, k_rollout and
+// k_rollout2.
 #include "st_internal.h"
+
+#if defined(ST_STEP_EXPORT_TU) || defined(ST_AFTERSTATES_TU)
+#define ST_SIDE_TU 1  // not the library's own translation unit
+#endif
 
 
 namespace st {
@@ -700,7 +706,8 @@ __device__ __forceinline__ int mt_chunk_store(const MtRes &rs, int lane, const M
 // (wave-uniform arguments): the chunked recurrence in LDS -- [0,227) reads old
 // words | [227,454) reads [0,227) | [454,623) reads [227,396) | 623 reads 396
 // and 0, each chunk only words that are old or finished.
-__device__ __attribute__((noinline)) void mt_finish(uint32_t *g, uint32_t *S, int lane, int pg, int cur) {
+// (maybe_unused: the afterstates translation unit draws nothing)
+[[maybe_unused]] __device__ __attribute__((noinline)) void mt_finish(uint32_t *g, uint32_t *S, int lane, int pg, int cur) {
     const uint32_t *src_new = g + (cur ? 0 : kMtB), *src_old = g + (cur ? kMtB : 0);
     uint32_t *dst = g + (cur ? 0 : kMtB);
     {
@@ -3125,7 +3132,7 @@ constexpr uint32_t kScoringFlags =
     ST_PENALISE_HEIGHT | ST_PENALISE_HEIGHT_INCREASE | ST_ADVANCED_CLEARS | ST_HIGH_SCORING |
     ST_PENALISE_HOLES | ST_PENALISE_HOLES_INCREASE;
 
-#ifndef ST_STEP_EXPORT_TU
+#ifndef ST_SIDE_TU
 // ---------------------------------------------------------------- reset
 // TetrisEngine.clear (tetris_env.py:306-315) on masked envs.  n_deaths,
 // shape_counts and the lock-delay counter persist (R15).
@@ -3305,7 +3312,7 @@ __global__ __launch_bounds__(kWave) void k_render(KParams p) {
     if (e < p.n)
         for (int x = 0; x < W; ++x) p.obs[x * p.n + e] = lcol(L, x, lane) & hmask;
 }
-#endif  // !ST_STEP_EXPORT_TU
+#endif  // !ST_SIDE_TU
 
 // ---------------------------------------------------------------- export
 // st_export_env: one env's outputs and state as one record (the single-env
@@ -3364,14 +3371,14 @@ __device__ __forceinline__ void export_record(const KParams &p, int64_t env, con
     }
 }
 
-#ifndef ST_STEP_EXPORT_TU
+#ifndef ST_SIDE_TU
 __global__ __launch_bounds__(256) void k_export(KParams p, int64_t env, const uint32_t *obs,
                                                const int32_t *rew, const uint8_t *done, uint32_t parts,
                                                uint32_t *out) {
     export_record(p, env, obs, rew, done, parts, out, (int)threadIdx.x, (int)blockDim.x);
 }
 
-#else  // ST_STEP_EXPORT_TU
+#elif defined(ST_STEP_EXPORT_TU)
 // st_step_export: k_step (packed outputs, no stamps, not gated) with the
 // export record of one env written by the workgroup that stepped it -- the
 // single-env surface's step and read-back in ONE launch.  Both waves run
@@ -3421,7 +3428,7 @@ __global__ __launch_bounds__(2 * kWave) void k_step_export(uint32_t *board, int3
 }
 #endif  // ST_STEP_EXPORT_TU
 
-#ifndef ST_STEP_EXPORT_TU
+#ifndef ST_SIDE_TU
 // ---------------------------------------------------------------- misc
 // Image writers: the output of a block of envs is one contiguous region, so
 // lanes walk it in 16-B chunks (lane-consecutive vector stores, one 1-KB
@@ -3881,7 +3888,134 @@ __global__ __launch_bounds__(kWave) void k_policy_greedy(KParams p, uint64_t see
     if ((uint32_t)(h % 1000ull) < explore) a = (uint32_t)((h >> 32) % 7ull);
     if (e < p.n) out[e] = (uint8_t)a;
 }
-#endif  // !ST_STEP_EXPORT_TU
+#endif  // !ST_SIDE_TU
+
+#ifdef ST_AFTERSTATES_TU
+// ---------------------------------------------------------------- afterstates
+// st_afterstates: what k_policy_greedy evaluates and throws away, as an
+// output.  For env e's board and current piece id, every placement slot
+// s = rot * (W + 6) + (x + 3) (k_policy_greedy's (rot, x) loop order): the
+// piece at (x, 0) in rotation rot is valid iff not is_occupied
+// (tetris_env.py:29-36), is hard-dropped (:54-59), set (_set_piece's
+// clipping, :323-327) and the full rows are cleared (:205-216); the rows of
+// st_after_feat and, optionally, the resulting board are written.  The
+// piece's present rot, anchor and lock counter play no part, nor does
+// lock_delay; no state is written.
+// One wave per env, lane = slot, ceil(S / 64) passes.  The env's W column
+// words are wave-uniform: lanes 0 .. W + 15 load one word each (floor bits,
+// all-ones walls, as k_policy_greedy stages them) into W + 16 LDS words, and
+// every later column read is a broadcast (all lanes one address) or, for the
+// four box columns, at most W + 16 distinct addresses.  Outputs have the slot
+// innermost, so each row leaves as one contiguous store per wave.
+// REWARD is lock_score's -- the rules of the step that locks the piece there
+// (:256-297) under the context's flags, from the env's holes and
+// piece_height counters.
+__global__ __launch_bounds__(kWave) void k_afterstates(KParams p, int32_t *__restrict__ feat,
+                                                       uint32_t *__restrict__ boards) {
+    constexpr int P = 8;  // wall columns each side: the box's columns span [-6, W + 5]
+    __shared__ uint32_t L[kMaxW + 2 * P];
+    const int lane = threadIdx.x;
+    const int64_t e = blockIdx.x;  // the grid is p.n waves: padding envs are not evaluated
+    const int64_t sd = p.stride;
+    const int W = p.W, H = p.H;
+    const uint32_t hmask = (1u << H) - 1u, floorb = ~hmask;
+    const int per = W + 6, S = 4 * per;
+    if (lane < W + 2 * P) {
+        const int c = lane - P;
+        L[lane] = c >= 0 && c < W ? p.board[c * sd + e] | floorb : ~0u;
+    }
+    const uint32_t pid = p.piece[e] & 7u;
+    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
+    const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
+    const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd + e];
+    wave_sync();
+    const size_t fbase = (size_t)e * ST_AFTER_NFEAT * S, bbase = (size_t)e * W * S;
+    for (int s0 = 0; s0 < S; s0 += kWave) {
+        const int s = s0 + lane;
+        const bool live = s < S;
+        const int sc = live ? s : S - 1;  // (lanes past the last slot compute it again, store nothing)
+        const int r = (sc >= per) + (sc >= 2 * per) + (sc >= 3 * per), x = sc - r * per - 3;
+        const uint32_t m = c_tab_m[id * 4 + r], g = c_tab_g[id * 4 + r];
+        const int x0 = box_x0(g, x);
+        uint32_t v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = L[x0 + j + P];
+        const bool valid = live && !collides_v(m, 0, v);
+        const int y = valid ? drop_box(g, 0, v) : 0;
+        bool above = false;
+        uint32_t pb[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t byte = (m >> (8 * j)) & 0xFFu;
+            above = above || (byte != 0u && y + __builtin_ctz(byte) - 3 < 0);  // (a box column without cells)
+            pb[j] = pc_bits(m, j, y) & hmask;
+        }
+        // the board with the piece: column c gets the bits of the box column at c
+        uint32_t andv = hmask;
+        for (int c = 0; c < W; ++c) {
+            uint32_t w = L[c + P];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
+            andv &= w;
+        }
+        const int32_t ncl = __builtin_popcount(andv);
+        int32_t holes = 0, agg = 0, bump = 0, hprev = 0;
+        uint32_t orv = 0;
+        for (int c = 0; c < W; ++c) {
+            uint32_t w = L[c + P] & hmask;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
+            if (andv) w = compact(w, andv);
+            const int32_t h = H - (int32_t)__builtin_ctz(w | floorb);  // the column's height
+            holes += h - __builtin_popcount(w);
+            agg += h;
+            bump += c ? (h > hprev ? h - hprev : hprev - h) : 0;
+            hprev = h;
+            orv |= w;
+            if (boards && live) boards[bbase + (size_t)c * S + s] = valid ? w : 0u;
+        }
+        int32_t rew = (p.flags & ST_REWARD_STEP) ? 1 : 0;  // :256
+        int32_t score = 0, lines = 0, nholes = 0, height = 0, deaths = 0;
+        lock_score<false>(p.flags, ncl, orv, [&] { return holes; }, old_holes, old_height, rew, score, lines, nholes,
+                          height, deaths);
+        if (live) {
+            int32_t *f = feat + fbase + s;
+            auto put = [&](int row, int32_t val) { f[(size_t)row * S] = valid ? val : 0; };
+            put(ST_AFTER_VALID, 1);
+            put(ST_AFTER_Y, y);
+            put(ST_AFTER_LINES, ncl);
+            put(ST_AFTER_HOLES, holes);
+            put(ST_AFTER_HEIGHT, orv ? H - (int32_t)__builtin_ctz(orv) : 0);
+            put(ST_AFTER_ROWS, __builtin_popcount(orv));
+            put(ST_AFTER_ABOVE, above ? 1 : 0);
+            put(ST_AFTER_DEAD, (int32_t)(orv & 1u));
+            put(ST_AFTER_REWARD, rew);
+            put(ST_AFTER_AGG_HEIGHT, agg);
+            put(ST_AFTER_BUMPINESS, bump);
+        }
+    }
+}
+
+// st_placement_actions: the primitive action that moves env e's live piece
+// toward slot slots[e] -- k_policy_greedy's rule (gen_golden.greedy_action):
+// rotate_left until the rotation matches, then move toward x, then hard-drop;
+// a slot outside [0, S) hard-drops.  One lane per env.
+__global__ __launch_bounds__(256) void k_placement_actions(KParams p, const int32_t *__restrict__ slots,
+                                                           uint8_t *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.n) return;
+    const int per = p.W + 6;
+    const uint32_t pw = p.piece[e];
+    const int rot = (int)((pw >> 3) & 3u), ax = (int)((pw >> 5) & 63u);
+    const int32_t s = slots[e];
+    uint32_t a = 2u;
+    if (s >= 0 && s < 4 * per) {
+        const int trot = s / per, tx = s - trot * per - 3;
+        a = rot != trot ? 4u : (ax < tx ? 1u : (ax > tx ? 0u : 2u));
+    }
+    out[e] = (uint8_t)a;
+}
+#endif  // ST_AFTERSTATES_TU
 
 }  // namespace
 
@@ -3901,7 +4035,17 @@ hipError_t launch_step_export(const KParams &p, int64_t env, uint32_t parts, uin
 #undef ST_STEP_EXPORT_ARGS
     return hipGetLastError();
 }
-#else  // !ST_STEP_EXPORT_TU
+#elif defined(ST_AFTERSTATES_TU)
+hipError_t launch_afterstates(const KParams &p, int32_t *feat, uint32_t *boards, hipStream_t s) {
+    hipLaunchKernelGGL(k_afterstates, dim3((unsigned)p.n), dim3(kWave), 0, s, p, feat, boards);  // one wave per env
+    return hipGetLastError();
+}
+
+hipError_t launch_placement_actions(const KParams &p, const int32_t *slots, uint8_t *out, hipStream_t s) {
+    hipLaunchKernelGGL(k_placement_actions, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p, slots, out);
+    return hipGetLastError();
+}
+#else  // the library's own translation unit
 
 hipError_t launch_seed(const KParams &p, hipStream_t s) {
     const int64_t blocks = (p.stride + 255) / 256;
@@ -4122,6 +4266,6 @@ hipError_t launch_export(const KParams &p, int64_t env, const uint32_t *obs, con
     return hipGetLastError();
 }
 
-#endif  // !ST_STEP_EXPORT_TU
+#endif  // the library's own translation unit
 
 }  // namespace st

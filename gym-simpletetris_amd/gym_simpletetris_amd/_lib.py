@@ -39,6 +39,10 @@ STAT = dict(time=0, score=1, lines=2, holes=3, piece_height=4, deaths=5, count0=
 NSTAT = 19
 MT_N = 624
 EXPORT_MT, EXPORT_OBS_F32 = 1, 2  # st_export_env parts
+# st_after_feat: the feature rows of st_afterstates, by name
+AFTER = dict(valid=0, y=1, lines=2, holes=3, height=4, rows=5, above=6, dead=7, reward=8, agg_height=9,
+             bumpiness=10)
+AFTER_NFEAT = 11
 
 
 class StError(RuntimeError):
@@ -100,6 +104,9 @@ SIG = {
     "st_stream_wait": ([_vp, _vp], ctypes.c_int),
     "st_gen_actions": ([_vp, _i64, _i64, _u64, _i64, _vp], ctypes.c_int),
     "st_policy_greedy": ([_vp, _u64, _i64, ctypes.c_uint32, _vp, _vp], ctypes.c_int),
+    "st_after_slots": ([_i32], ctypes.c_int),
+    "st_afterstates": ([_vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_placement_actions": ([_vp, _vp, _vp, _vp], ctypes.c_int),
     "st_debug_stamps": ([_vp, _vp, _i64], ctypes.c_int),
     "st_last_error": ([], ctypes.c_char_p),
     "st_abi_version": ([], ctypes.c_int),
@@ -133,7 +140,7 @@ def load(path: str = LIB_PATH):
         if not hasattr(L, name):
             if ab_override:
                 continue
-            # an addition that did not change the ABI number (st_step_export):
+            # an addition that did not change the ABI number (st_step_export, st_afterstates):
             # the library on disk was built before it
             raise ImportError(f"{path}: no symbol {name} (a stale build of ABI {abi}: rebuild it with "
                               "`make -C gym-simpletetris_amd/csrc`)")

@@ -142,6 +142,38 @@ def _from_dlpack(x):
     return torch.from_dlpack(x)
 
 
+def placement_slot(width: int, rot: int, x: int) -> int:
+    """The placement slot of rotation `rot` (0..3 applications of
+    rotated(cclk=False), tetris_env.py:22-26) at anchor column `x`
+    (-3..width+2) on a board `width` wide: rot * (width + 6) + (x + 3),
+    st_policy_greedy's (rot, x) loop order."""
+    if not (0 <= rot < 4 and -3 <= x < width + 3):
+        raise ValueError(f"rot {rot} outside 0..3 or x {x} outside -3..{width + 2}")
+    return rot * (width + 6) + (x + 3)
+
+
+def placement_rot_x(width: int, slot: int):
+    """placement_slot's inverse: (rot, x) of a slot in [0, 4 * (width + 6))."""
+    if not 0 <= slot < 4 * (width + 6):
+        raise ValueError(f"slot {slot} outside [0, {4 * (width + 6)})")
+    return slot // (width + 6), slot % (width + 6) - 3
+
+
+class Afterstates:
+    """TetrisBatch.afterstates()'s result: `feat` int32 [n, AFTER_NFEAT, S] and
+    `boards` int32 [n, W, S] (or None), slot innermost; every feature row by
+    its name in _lib.AFTER as an [n, S] view of feat (.valid, .lines, ...)."""
+
+    def __init__(self, feat: torch.Tensor, boards: Optional[torch.Tensor]):
+        self.feat, self.boards = feat, boards
+
+    def __getattr__(self, name):  # (only names not found otherwise)
+        row = C.AFTER.get(name)
+        if row is None:
+            raise AttributeError(name)
+        return self.feat[:, row]
+
+
 class TetrisBatch:
     """Batched engine.  `autoreset`: 'none' (exact reference semantics; the
     caller resets done envs, like `if done: env.reset()`) or 'same_step'
@@ -219,6 +251,7 @@ class TetrisBatch:
         self.reward = torch.zeros(n, dtype=torch.int32, device=device)
         self.done = torch.zeros(n, dtype=torch.bool, device=device)
         self._act = torch.zeros(n, dtype=torch.uint8, device=device)
+        self._place_act: Optional[torch.Tensor] = None  # placement_actions' reused output (made on first use)
         self._seeded = False
         if seeds is not None:
             self.seed(seeds)
@@ -634,6 +667,72 @@ class TetrisBatch:
         with torch.cuda.device(self.device):
             C.check(self._L.st_gen_actions(_ptr(out), self.n, int(t), ctypes.c_uint64(seed),
                                            int(global_offset), self._stream()))
+        return out
+
+    # ------------------------------------------------------------ afterstates
+    @property
+    def n_slots(self) -> int:
+        """Placement slots per env: 4 * (width + 6) (st_after_slots)."""
+        return 4 * (self.width + 6)
+
+    def slot(self, rot: int, x: int) -> int:
+        return placement_slot(self.width, rot, x)
+
+    def slot_rot_x(self, slot: int):
+        return placement_rot_x(self.width, slot)
+
+    def afterstates(self, boards: bool = True, out=None) -> Afterstates:
+        """Every placement of every env's current piece, in one launch
+        (st_afterstates): slot s = slot(rot, x) is the piece in rotation rot
+        at anchor (x, 0), valid iff not is_occupied there (tetris_env.py:29-36),
+        hard-dropped (:54-59), set (:323-327) and the lines cleared (:205-216).
+        Returns an Afterstates: feat int32 [n, AFTER_NFEAT, S], rows by name
+        (.valid, .y, .lines, .holes, .height, .rows, .above, .dead, .reward,
+        .agg_height, .bumpiness: _lib.AFTER), and with `boards` the resulting
+        column words int32 [n, W, S] (else None); all zero for an invalid
+        slot.  .reward is the reward of the step that locks the piece there,
+        under this batch's scoring flags.  It is the idealised placement the
+        greedy policy scores: no promise that moves, rotations and gravity can
+        bring the live piece there.  Reads the state, changes none of it.
+        `out`: a (feat, boards) pair of device tensors to write (boards None
+        without `boards`)."""
+        n, W, S = self.n, self.width, self.n_slots
+        if out is None:
+            feat = torch.empty((n, C.AFTER_NFEAT, S), dtype=torch.int32, device=self.device)
+            brd = torch.empty((n, W, S), dtype=torch.int32, device=self.device) if boards else None
+        else:
+            feat, brd = out
+            _check_tensor(feat, "out feat", (n, C.AFTER_NFEAT, S), (torch.int32,), self.device)
+            if boards:
+                _check_tensor(brd, "out boards", (n, W, S), (torch.int32,), self.device)
+            elif brd is not None:
+                raise ValueError("out boards given with boards=False")
+        C.check(self._L.st_afterstates(self._ctx, _ptr(feat), _ptr(brd), self._stream()))
+        return Afterstates(feat, brd)
+
+    def placement_actions(self, slots, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The action (uint8 [n], as step() takes it) that moves each env's
+        live piece toward its placement slot (st_placement_actions):
+        rotate_left (4) until the rotation is the slot's, then right (1) /
+        left (0) toward its column, then hard drop (2) -- the greedy
+        policy's rule; a slot outside [0, n_slots) (e.g. -1: no valid
+        placement) hard-drops.  slots: [n] integers, a device tensor (int32
+        as it is) or a host sequence."""
+        if isinstance(slots, torch.Tensor):
+            if slots.is_floating_point() or slots.is_complex() or slots.dtype == torch.bool:
+                raise TypeError(f"slots must be integers, got {slots.dtype}")
+            s = slots.to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            s = torch.as_tensor(np.asarray(slots).astype(np.int32), device=self.device)
+        if tuple(s.shape) != (self.n,):
+            raise ValueError(f"slots must have shape ({self.n},), got {tuple(s.shape)}")
+        if out is None:
+            if self._place_act is None:
+                self._place_act = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+            out = self._place_act
+        else:
+            _check_tensor(out, "out", (self.n,), (torch.uint8,), self.device)
+        C.check(self._L.st_placement_actions(self._ctx, _ptr(s), _ptr(out), self._stream()))
         return out
 
 

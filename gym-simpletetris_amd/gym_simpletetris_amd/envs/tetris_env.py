@@ -534,6 +534,18 @@ class TetrisVecEnv:
         reached any step so far (waits for the queued work)."""
         self.engine.check_actions()
 
+    def afterstates(self, boards: bool = True, out=None):
+        """TetrisBatch.afterstates of the engine, on its stream: every
+        placement of every env's current piece (features and boards), for an
+        afterstate agent's afterstates -> score -> argmax ->
+        placement_actions -> step loop."""
+        return self.engine.afterstates(boards=boards, out=out)
+
+    def placement_actions(self, slots, out=None):
+        """TetrisBatch.placement_actions of the engine, on its stream: the
+        uint8 actions step() takes, toward the chosen placement slots."""
+        return self.engine.placement_actions(slots, out=out)
+
     def close(self):
         self._pool.clear()
         self.engine.close()

@@ -35,7 +35,8 @@ extern "C" {
  * word for 10x20), st_unwire_shards.  3: st_gate_actions / st_gate_wait,
  * st_stream_wait (additions only).  4: st_step_n (addition only).
  * st_step_export: addition only, version unchanged (a build without it is
- * refused by the host package when it binds the symbol).
+ * refused by the host package when it binds the symbol); so are
+ * st_after_slots / st_afterstates / st_placement_actions.
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -322,6 +323,63 @@ int st_load(st_ctx *ctx, const void *host_in, int64_t bytes);
  * enqueued before it on `stream`. */
 int st_policy_greedy(st_ctx *ctx, uint64_t seed, int64_t t, uint32_t explore_permille,
                      uint8_t *d_actions, st_stream stream);
+
+/* Afterstates: what every placement of env e's current piece would lead to,
+ * the input of afterstate value functions and feature players (Dellacherie /
+ * BCTS, CEM over feature weights), evaluated on the device in one launch.
+ *
+ * Placement slots of a board of width W: slot = rot * (W + 6) + (x + 3), rot
+ * 0..3 applications of rotated(cclk=False) (tetris_env.py:22-26, as in the
+ * piece word), anchor x in -3..W+2; S = st_after_slots(W) = 4 * (W + 6) slots
+ * in st_policy_greedy's (rot, x) order.
+ *
+ * The afterstate of a slot takes the env's current board and current piece
+ * id only (the piece's present rot, anchor and lock counter play no part, nor
+ * does lock_delay).  The slot is VALID iff not is_occupied(cells, (x, 0),
+ * board) (:29-36; cells above row 0 do not count, so a placement hanging off
+ * the board above the top is valid, as in the reference).  The piece is then
+ * hard-dropped from row 0 (:54-59), set with _set_piece's clipping (:323-327)
+ * and _clear_lines runs (:205-216).  This is the idealised placement
+ * st_policy_greedy scores: NOT a promise that a sequence of moves, rotations
+ * and gravity steps can bring the live piece there.
+ *
+ * Feature rows (int32; every row, and the board, of an invalid slot is 0): */
+enum st_after_feat {
+    ST_AFTER_VALID,      /* 1 / 0 */
+    ST_AFTER_Y,          /* anchor row after the drop */
+    ST_AFTER_LINES,      /* rows cleared */
+    ST_AFTER_HOLES,      /* _count_holes (:218-220) of the board after the clear */
+    ST_AFTER_HEIGHT,     /* height - topmost occupied row, 0 if empty (st_policy_greedy's height) */
+    ST_AFTER_ROWS,       /* sum(np.any(board, axis=0)): the reference's height (:287, :289) */
+    ST_AFTER_ABOVE,      /* 1 if a cell of the piece lay above row 0 (clipped at :326) */
+    ST_AFTER_DEAD,       /* np.any(board[:, 0]) after the clear (:277) */
+    ST_AFTER_REWARD,     /* the reward TetrisEngine.step returns for the step that locks the
+                            piece there (:256-297): under the context's scoring flags, from the
+                            env's current holes and piece_height counters, reward_step
+                            included, -100 on death */
+    ST_AFTER_AGG_HEIGHT, /* sum of column heights h[x] = height - topmost occupied row of column x (0 if empty) */
+    ST_AFTER_BUMPINESS,  /* sum |h[x] - h[x + 1]| */
+    ST_AFTER_NFEAT
+};
+/* 4 * (width + 6); ST_EINVAL for a width outside 4..32. */
+int st_after_slots(int32_t width);
+/* d_feat   : int32 [n_envs][ST_AFTER_NFEAT][S], required.
+ * d_boards : uint32 [n_envs][width][S] or NULL; word (e, x, s) is column x of
+ *            slot s's afterstate in the bit layout of st_state_views.board,
+ *            before any death-step erase (:303).
+ * Both have the slot innermost.  Reads the state enqueued before it on
+ * `stream` and changes none of it (board, piece, counters, MT); needs no
+ * st_mt_sync; is not gated and consumes no gate.  ST_EINVAL for a NULL ctx or
+ * d_feat, ST_ESTATE before st_seed + st_reset, both before any GPU call. */
+int st_afterstates(st_ctx *ctx, int32_t *d_feat, uint32_t *d_boards, st_stream stream);
+/* d_actions[e] (uint8 [n_envs]) = the primitive action that moves env e's live
+ * piece toward slot d_slots[e] (int32 [n_envs]): 4 (rotate_left) if its rot
+ * differs from the slot's, else 1 / 0 if its anchor x is left / right of the
+ * slot's, else 2 (hard drop); a slot outside [0, S) gives 2.  This is
+ * st_policy_greedy's rule: afterstates -> score -> argmax ->
+ * st_placement_actions -> st_step, repeated, plays the chosen placement out.
+ * NULL checks and ST_ESTATE as for st_afterstates. */
+int st_placement_actions(st_ctx *ctx, const int32_t *d_slots, uint8_t *d_actions, st_stream stream);
 
 /* Synthetic action source used by the benchmark and the parity tests:
  * d_out[e] = splitmix64(seed ^ ((t << 32) ^ (global_offset + e))) % 7. */
