@@ -21,6 +21,9 @@ Fixtures:
   grayscale.npz        F5  convert_grayscale images (next row, R19)
   render.npz           F5b engine.render(), render("rgb_array") and grayscale/rgb obs
                            along uniform-action games (python gen_golden.py render)
+  truncated.npz        F6  uniform-action games whose live envs are reset at random
+                           (time-limit truncations), the state after every reset
+                           (python gen_golden.py truncated)
 (python gen_golden.py crafted writes crafted.npz alone.)
 
 Usage: python tests/golden/gen_golden.py  (writes next to this file)
@@ -523,7 +526,101 @@ def gen_render():
     np.savez_compressed(os.path.join(HERE, "render.npz"), **blob)
 
 
-GENERATORS = ("mt", "crafted", "rollouts", "greedy", "grayscale", "render")
+# ---------------------------------------------------------------- F6
+_C4 = dict(advanced_clears=True, penalise_holes_increase=True, penalise_height_increase=True)
+TRUNC_CONFIGS = (
+    ("lock2_reset_c4", dict(lock_delay=2, step_reset=True, **_C4)),
+    ("lock3_9x15", dict(width=9, height=15, lock_delay=3, high_scoring=True, penalise_height=True,
+                        penalise_holes=True)),
+    ("lock0_c4", dict(_C4)),
+    ("lock1_reset_5x27", dict(width=5, height=27, lock_delay=1, step_reset=True)),
+    ("lock40_7x12", dict(width=7, height=12, lock_delay=40)),
+)
+TRUNC_P, TRUNC_SEED_BASE, TRUNC_ACTION_SEED = 0.04, 900, 0xD00D
+TRUNC_MIN, TRUNC_MIN_LOCKED = 50, 10  # per configuration: truncations of live envs; of those, lock counter != 0
+TRUNC_INFO = ("time", "score", "lines_cleared", "holes", "deaths")
+
+
+def run_truncated(n_envs, steps, cfg, seed_base, action_seed):
+    """run_rollouts' uniform-action games with time-limit truncations: after
+    each step of env e one draw decides whether the env is reset although it
+    lives (one draw per env-step, in env order, dead or not); a dead env is
+    reset as always.  Besides the Recorder fields of every step: `reset`, the
+    state after the step's reset if any (after_*), and where a reset happened
+    engine.render() straight after it and reset(return_info=True)'s info."""
+    envs = [make_env(cfg) for _ in range(n_envs)]
+    W = envs[0].engine.width
+    states = []
+    for e in range(n_envs):
+        random.seed(seed_base + e)
+        envs[e].reset()
+        states.append(random.getstate())
+    rec = [Recorder() for _ in range(n_envs)]
+    acts = splitmix64_actions(action_seed, 0, steps, n_envs)
+    prng = np.random.default_rng(action_seed)
+    out = {"actions": acts, "reset": np.zeros((steps, n_envs), bool),
+           "after_piece": np.zeros((steps, n_envs), np.uint32), "after_time": np.zeros((steps, n_envs), np.int32),
+           "after_counts": np.zeros((steps, n_envs, 7), np.int32),
+           "after_board": np.zeros((steps, n_envs, W), np.uint32),
+           "after_render": np.zeros((steps, n_envs, W), np.uint32),
+           "reset_piece": np.zeros((steps, n_envs), np.int32),
+           "reset_counts": np.zeros((steps, n_envs, 7), np.int32)}
+    for k in TRUNC_INFO:
+        out["reset_" + k] = np.zeros((steps, n_envs), np.int32)
+    locked = 0
+    for t in range(steps):
+        for e in range(n_envs):
+            env, eng = envs[e], envs[e].engine
+            random.setstate(states[e])
+            obs, r, d, info = env.step(int(acts[t, e]))
+            rec[e].add(env, obs, r, d, info)
+            trunc = bool(prng.random() < TRUNC_P)
+            if d or trunc:
+                locked += int(not d and eng._lock_delay != 0)
+                obs0, rinfo = env.reset(return_info=True)
+                assert not obs0.any()
+                out["reset"][t, e] = True
+                out["after_render"][t, e] = pack_cols(eng.render())
+                for k in TRUNC_INFO:
+                    out["reset_" + k][t, e] = int(rinfo[k])
+                out["reset_piece"][t, e] = SHAPE_NAMES.index(rinfo["current_piece"])
+                out["reset_counts"][t, e] = [int(rinfo["statistics"][k]) for k in SHAPE_NAMES]
+            out["after_piece"][t, e] = pack_piece(eng)
+            out["after_time"][t, e] = int(eng.time)
+            out["after_counts"][t, e] = [int(eng.shape_counts[k]) for k in SHAPE_NAMES]
+            out["after_board"][t, e] = pack_cols(eng.board)
+            states[e] = random.getstate()
+    for k in Recorder.FIELDS:
+        out[k] = np.stack([np.array(rec[e].rows[k]) for e in range(n_envs)], axis=1)
+    return out, locked
+
+
+def gen_truncated(n_envs=8, steps=400):
+    blob, meta = {}, {}
+    for i, (name, cfg) in enumerate(TRUNC_CONFIGS):
+        seed_base, action_seed = TRUNC_SEED_BASE + 97 * i, TRUNC_ACTION_SEED + i
+        d, locked = run_truncated(n_envs, steps, cfg, seed_base, action_seed)
+        trunc = d["reset"] & ~d["done"].astype(bool)
+        assert (d["reset"] | ~d["done"].astype(bool)).all()
+        assert int(trunc.sum()) >= TRUNC_MIN, (name, int(trunc.sum()))
+        # the counter a truncation hands to the next episode is the recorded one
+        assert locked == int(((d["after_piece"] >> 17 != 0) & trunc).sum())
+        assert not cfg.get("lock_delay") or locked >= TRUNC_MIN_LOCKED, (name, locked)
+        for k, v in d.items():
+            dt = {"reward": np.int32, "rtype": np.uint8, "done": np.uint8, "piece": np.uint32, "obs": np.uint32,
+                  "board": np.uint32, "actions": np.uint8, "reset": np.bool_, "after_piece": np.uint32,
+                  "after_board": np.uint32, "after_render": np.uint32}.get(k, np.int32)
+            blob[f"{name}/{k}"] = v.astype(dt)
+        meta[name] = dict(cfg=cfg, seed_base=seed_base, action_seed=action_seed, n_envs=n_envs, steps=steps,
+                          policy="uniform+truncation", dones=int(d["done"].sum()), truncations=int(trunc.sum()),
+                          truncations_locked=locked)
+        print("truncated", name, meta[name]["dones"], "dones", meta[name]["truncations"], "truncations",
+              locked, "with a non-zero lock counter")
+    blob["meta"] = np.array(json.dumps(meta))
+    np.savez_compressed(os.path.join(HERE, "truncated.npz"), **blob)
+
+
+GENERATORS = ("mt", "crafted", "rollouts", "greedy", "grayscale", "render", "truncated")
 
 
 def main(which=GENERATORS):
@@ -533,7 +630,9 @@ def main(which=GENERATORS):
     ref = load_reference()
     if "render" in which:
         gen_render()
-    rest = set(which) - {"render"}
+    if "truncated" in which:
+        gen_truncated()
+    rest = set(which) - {"render", "truncated"}
     if not rest:
         return
     if rest == {"crafted"}:
@@ -549,6 +648,7 @@ def main(which=GENERATORS):
 
 
 if __name__ == "__main__":
-    # no arguments: every fixture; else a subset of GENERATORS ("render" and
-    # "crafted" are generated on their own, the others are written together)
+    # no arguments: every fixture; else a subset of GENERATORS ("render",
+    # "truncated" and "crafted" are generated on their own, the others are
+    # written together)
     main(tuple(sys.argv[1:]) or GENERATORS)

@@ -81,6 +81,78 @@ def mt_twist(words):
     return w
 
 
+def untemper(y):
+    """Inverse of MT19937 tempering (so crafted state words produce chosen outputs)."""
+    def undo_r(y, s):
+        x = y
+        for _ in range(32 // s + 1):
+            x = y ^ (x >> s)
+        return x & 0xFFFFFFFF
+
+    def undo_l(y, s, m):
+        x = y
+        for _ in range(32 // s + 1):
+            x = y ^ ((x << s) & m)
+        return x & 0xFFFFFFFF
+    y = undo_r(y, 18)
+    y = undo_l(y, 15, 0xEFC60000)
+    y = undo_l(y, 7, 0x9D2C5680)
+    return undo_r(y, 11)
+
+
+# ------------------------------------------------------------------ the replay adapter
+class HipAdapter:
+    """TetrisBatch(autoreset='none') behind the replay interface (replay.py).
+    sync=False reads board, piece and counter rows without st_mt_sync (they
+    are exact without it), so every env keeps the preview the step kernels
+    drew one spawn ahead and a reset consumes it; sync=True (get_state) gives
+    every preview back after every step, and a reset draws its piece afresh."""
+
+    def __init__(self, n, seeds, kw, sync=True):
+        self.b = engine().TetrisBatch(n, autoreset="none", seeds=seeds, **kw)
+        self.n, self.sync = n, sync
+
+    def _dev(self, a):
+        import torch
+        return torch.as_tensor(np.asarray(a, np.uint8), device=self.b.device)
+
+    def _read(self):
+        if self.sync:
+            return self.b.get_state(("board", "piece", "stats"))
+        st = {k: v.cpu().numpy()[..., :self.n] for k, v in
+              self.b.state_tensors(("board", "piece", "stats"), sync=False).items()}
+        return dict(st, board=st["board"].view(np.uint32), piece=st["piece"].view(np.uint32))
+
+    def reset(self, mask):
+        self.b.reset(None if bool(np.all(mask)) else self._dev(mask))
+
+    def set_state(self, i, init):
+        st = self.b.get_state(("board", "piece", "stats"))
+        st["board"][:, i] = init["board"]
+        st["piece"][i] = init["piece"]
+        s = st["stats"]
+        s[0, i], s[1, i], s[2, i], s[3, i] = init["time"], init["score"], init["lines"], init["holes"]
+        s[4, i], s[5, i] = init["height"], init["deaths"]
+        s[6:13, i] = init["counts"]
+        self.b.set_state(**st)
+
+    def step(self, actions):
+        obs, rew, done = self.b.step(self._dev(actions), obs="packed")
+        st = self._read()
+        s = st["stats"]
+        return dict(reward=rew.cpu().numpy(), done=done.cpu().numpy().astype(np.uint8),
+                    time=s[0], score=s[1], lines=s[2], holes=s[3], height=s[4], deaths=s[5],
+                    counts=s[6:13].T, piece=st["piece"],
+                    obs=words(obs), board=st["board"].T)
+
+    def state(self):
+        st = self._read()
+        return dict(piece=st["piece"], time=st["stats"][0], counts=st["stats"][6:13].T, board=st["board"].T)
+
+    def render(self):
+        return words(self.b.render_packed())
+
+
 # ------------------------------------------------------------------ action streams
 def wall_pattern(W, steps, n):
     """actions [steps, n]: env i repeats W // 2 + 1 moves towards one wall
@@ -255,6 +327,14 @@ def check_final_observation(info, robs, done, t, H=None):
 def engine_state(b, fields=("board", "piece", "stats", "mt")):
     """A copy of a batch's (or a vector env's engine's) state."""
     return {k: v.copy() for k, v in getattr(b, "engine", b).get_state(fields).items()}
+
+
+def raw_state(b):
+    """The state as it lies in device memory, padding envs and both MT
+    generation buffers included, read without st_mt_sync: the read changes
+    nothing (previews and generations in progress stay as they are)."""
+    t = getattr(b, "engine", b).state_tensors(("board", "piece", "stats", "mt"), sync=False)
+    return {k: v.cpu().numpy() for k, v in t.items()}
 
 
 def assert_same_state(a, b, what="", fields=("board", "piece", "stats", "mt")):

@@ -6,6 +6,9 @@ An *adapter* wraps one batched engine and exposes:
     set_state(i, init)      -- load a crafted initial state (board/piece/counters)
     step(actions) -> dict   -- one reference step on every env, NO auto-reset;
                                returns per-env arrays keyed like Recorder.FIELDS
+    state() -> dict         -- piece word, time, shape counts and board of every
+                               env as they are now (replay_truncated)
+    render() -> [n, W]      -- TetrisEngine.render() as column words (replay_truncated)
 The replay loop mirrors the fixture driver in gen_golden.py: step all envs,
 compare, then reset the envs that reported done (reference `if done: reset()`).
 """
@@ -64,6 +67,38 @@ def replay_rollout(adapter_factory, name, meta, arrs, fields=COMPARE, steps=None
         if done.any():
             ad.reset(done)
     return T * n
+
+
+AFTER = ("piece", "time", "counts", "board")
+
+
+def replay_truncated(adapter_factory, name, meta, arrs, fields=COMPARE):
+    """The truncation fixture (gen_golden.py run_truncated): step, compare,
+    reset the envs the reference reset -- the dead ones and the live ones its
+    time limit cut off -- then compare adapter.state() (piece word, time,
+    shape counts, board) with the state the reference had behind the step's
+    resets, and adapter.render() [n, W] with engine.render() straight after
+    reset() in the envs that were reset."""
+    n = meta["n_envs"]
+    seeds = [meta["seed_base"] + e for e in range(n)]
+    ad = adapter_factory(n, seeds, engine_kwargs(meta["cfg"]))
+    ad.reset(np.ones(n, bool))
+    after = {k: arrs["after_" + k] for k in AFTER}
+    resets = 0
+    for t in range(arrs["actions"].shape[0]):
+        got = ad.step(arrs["actions"][t])
+        _check(name, t, got, arrs, fields)
+        mask = arrs["reset"][t].astype(bool)
+        assert not (np.asarray(got["done"]).astype(bool) & ~mask).any()  # a dead env is always reset
+        if mask.any():
+            ad.reset(mask)
+            resets += int(mask.sum())
+            render = np.asarray(ad.render())
+            assert np.array_equal(render[mask], arrs["after_render"][t][mask]), f"{name}: step {t} render after reset"
+        st = ad.state()
+        assert sorted(st) == sorted(AFTER)
+        _check(f"{name} (after reset)", t, st, after, AFTER)
+    return resets
 
 
 def replay_crafted(adapter_factory, name, meta, arrs, fields=COMPARE):

@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 import torch
 
-from harness import (C4, assert_same_state, batch_and_oracle, check_mt_state, check_step, check_steps,
-                     engine as _engine, engine_state, mt_twist, set_mt_state, unpack_f32, words)
+from harness import (C4, HipAdapter, assert_same_state, batch_and_oracle, check_mt_state, check_step, check_steps,
+                     engine as _engine, engine_state, mt_twist, set_mt_state, unpack_f32, untemper, words)
 from oracle import oracle as O
 from replay import GOLDEN, load_set, replay_crafted, replay_rollout
 
@@ -25,39 +25,6 @@ RENDER = load_set("render.npz")
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a ROCm device")
-
-
-class HipAdapter:
-    """TetrisBatch(autoreset='none') behind the replay interface."""
-
-    def __init__(self, n, seeds, kw):
-        G = _engine()
-        self.b = G.TetrisBatch(n, autoreset="none", seeds=seeds, **kw)
-        self.n = n
-
-    def reset(self, mask):
-        m = torch.as_tensor(np.asarray(mask, np.uint8), device=self.b.device)
-        self.b.reset(None if bool(np.all(mask)) else m)
-
-    def set_state(self, i, init):
-        st = self.b.get_state(("board", "piece", "stats"))
-        st["board"][:, i] = init["board"]
-        st["piece"][i] = init["piece"]
-        s = st["stats"]
-        s[0, i], s[1, i], s[2, i], s[3, i] = init["time"], init["score"], init["lines"], init["holes"]
-        s[4, i], s[5, i] = init["height"], init["deaths"]
-        s[6:13, i] = init["counts"]
-        self.b.set_state(**st)
-
-    def step(self, actions):
-        obs, rew, done = self.b.step(torch.as_tensor(np.asarray(actions, np.uint8),
-                                                     device=self.b.device), obs="packed")
-        st = self.b.get_state(("board", "piece", "stats"))
-        s = st["stats"]
-        return dict(reward=rew.cpu().numpy(), done=done.cpu().numpy().astype(np.uint8),
-                    time=s[0], score=s[1], lines=s[2], holes=s[3], height=s[4], deaths=s[5],
-                    counts=s[6:13].T, piece=st["piece"],
-                    obs=words(obs), board=st["board"].T)
 
 
 def test_library_is_the_hip_build():
@@ -728,25 +695,6 @@ def test_rollout_vs_oracle_full_size():
     check_steps(ref, *b.rollout(torch.as_tensor(acts, device=b.device)))
 
 
-def _untemper(y):
-    """Inverse of MT19937 tempering (so crafted state words produce chosen outputs)."""
-    def undo_r(y, s):
-        x = y
-        for _ in range(32 // s + 1):
-            x = y ^ (x >> s)
-        return x & 0xFFFFFFFF
-
-    def undo_l(y, s, m):
-        x = y
-        for _ in range(32 // s + 1):
-            x = y ^ ((x << s) & m)
-        return x & 0xFFFFFFFF
-    y = undo_r(y, 18)
-    y = undo_l(y, 15, 0xEFC60000)
-    y = undo_l(y, 7, 0x9D2C5680)
-    return undo_r(y, 11)
-
-
 @pytest.mark.parametrize("mode", ["step", "rollout"])
 def test_long_rejection_runs_and_twists(mode):
     """Crafted MT states: draws that reject 10 words in a row (the second
@@ -757,7 +705,7 @@ def test_long_rejection_runs_and_twists(mode):
     b, ob = batch_and_oracle(n, range(n))
     st = b.get_state(("mt", "stats"))
     mt, stats = st["mt"].copy(), st["stats"].copy()
-    rej, acc = _untemper(0xFFFFFFFF), _untemper(0)
+    rej, acc = untemper(0xFFFFFFFF), untemper(0)
     for i in range(n):
         idx = int(stats[13, i])
         if i % 4 == 0 and idx + 21 <= 624:          # 20 rejections, then accept
@@ -840,7 +788,7 @@ def test_sync_at_generation_boundary(mode):
     b, ob = batch_and_oracle(n, range(100, 100 + n))
     st = b.get_state(("mt", "stats"))
     mt, stats = st["mt"].copy(), st["stats"].copy()
-    acc = _untemper(0)                  # accepted by any randint range
+    acc = untemper(0)                  # accepted by any randint range
     mt[:, 623] = acc
     stats[13] = 623
     set_mt_state(ob, mt, stats[13])

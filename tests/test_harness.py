@@ -56,6 +56,19 @@ def test_mt_twist_is_cpythons_refill(seed):
     assert np.array_equal(got[0], got[1])
 
 
+def test_untemper_inverts_cpythons_tempering():
+    """A state word untemper(y) at CPython's index comes out as y: the crafted
+    MT states' all-ones words are rejected by every randint range, their zero
+    words accepted."""
+    r = random.Random(9)
+    st = r.getstate()
+    want = [0xFFFFFFFF, 0, 0x12345678, 0x80000001]
+    words = list(st[1][:624])
+    words[5:9] = [Hn.untemper(y) for y in want]
+    r.setstate((st[0], tuple(words) + (5,), st[2]))
+    assert [r.getrandbits(32) for _ in want] == want
+
+
 @pytest.mark.parametrize("H", [4, 20, 28])
 def test_unpack_f32_pack_cols_round_trip(H):
     cells = np.random.default_rng(H).integers(0, 2, (3, 7, H)).astype(np.uint8)
