@@ -1,5 +1,6 @@
-// st_afterstates.hip -- k_afterstates (st_afterstates) and k_placement_actions
-// (st_placement_actions) as a translation unit of their own: the kernels and
+// st_afterstates.hip -- k_afterstates (st_afterstates), k_placement_actions
+// (st_placement_actions), k_policy_linear and k_play_sum (st_policy_linear,
+// st_play_linear) as a translation unit of their own: the kernels and
 // their launchers live in st_kernels.hip beside the piece table and the
 // collision / drop / clear / scoring helpers they share with the step
 // kernels, and are compiled here, apart from them, so that adding them leaves

@@ -2,6 +2,8 @@
 // Declared in include/simpletetris.h; each entry point cites the reference
 // method it replaces there.  Owns the device state; launches the kernels of
 // st_kernels.hip on the caller's stream.
+#include <algorithm>
+
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,6 +36,10 @@ struct st_ctx {
     uint32_t gate_epoch;
     bool gate_armed;
     bool gate_pending;
+    // st_play_linear: one allocation made on first use -- a ring of reward
+    // rows int32 [R][n], the policy's actions uint8 [n], a ring of done rows
+    // uint8 [R][n]
+    int32_t *play_buf;
 };
 
 namespace {
@@ -100,6 +106,8 @@ void free_state(st_ctx *c) {
     if (c->gate) (void)hipFree(c->gate);
     if (c->gate_host) (void)hipHostFree(c->gate_host);
     if (c->gate_ev) (void)hipEventDestroy(c->gate_ev);
+    if (c->play_buf) (void)hipFree(c->play_buf);
+    c->play_buf = nullptr;
     c->gate = c->gate_host = c->gate_host_dev = nullptr;
     c->gate_ev = nullptr;
     c->stamps = nullptr;
@@ -205,7 +213,7 @@ int st_reset(st_ctx *c, const uint8_t *d_mask, st_stream stream) {
 
 static int step_impl(st_ctx *c, const uint8_t *d_actions, uint32_t *d_obs, float *d_obs_f32,
                      int32_t *d_reward, uint8_t *d_done, st_stream stream, uint32_t *d_final_obs = nullptr,
-                     int32_t *d_info = nullptr) {
+                     int32_t *d_info = nullptr, bool gated = true) {
     if (!c || !d_actions) return fail(ST_EINVAL, "st_step: null argument");
     if (!c->seeded || !c->reset_once)
         return fail(ST_ESTATE, "st_step before st_seed + st_reset (tetris_env.py:244 needs an anchor)");
@@ -218,7 +226,9 @@ static int step_impl(st_ctx *c, const uint8_t *d_actions, uint32_t *d_obs, float
     p.done = d_done;
     p.final_obs = d_final_obs;
     p.info = d_info;
-    if (c->gate_armed) {  // st_gate_actions ran for this step: skip it all if it saw a bad action
+    // st_gate_actions ran for this step: skip it all if it saw a bad action
+    // (gated false: st_play_linear's steps, whose actions are not the gate's -- it stays armed)
+    if (gated && c->gate_armed) {
         p.gate = c->gate;
         p.gate_epoch = c->gate_epoch;
         c->gate_armed = false;
@@ -543,6 +553,66 @@ int st_placement_actions(st_ctx *c, const int32_t *d_slots, uint8_t *d_actions, 
     if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_placement_actions before st_seed + st_reset");
     DeviceGuard g(c->device);
     ST_HIP(st::launch_placement_actions(params(c), d_slots, d_actions, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_policy_linear(st_ctx *c, const float *d_weights, int64_t n_w, int32_t *d_slots, uint8_t *d_actions,
+                     float *d_scores, int32_t *d_best, st_stream stream) {
+    if (!c || !d_weights) return fail(ST_EINVAL, "st_policy_linear: null argument");
+    if (n_w < 1) return fail(ST_EINVAL, "st_policy_linear: n_w %lld < 1", (long long)n_w);
+    if (!d_slots && !d_actions && !d_scores && !d_best) return fail(ST_EINVAL, "st_policy_linear: every output is null");
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_policy_linear before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_policy_linear: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_policy_linear(params(c), d_weights, n_w, d_slots, d_actions, d_scores, d_best,
+                                    (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_play_linear(st_ctx *c, const float *d_weights, int64_t n_w, int64_t k, int64_t *d_return, int32_t *d_episodes,
+                   uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream) {
+    if (!c || !d_weights) return fail(ST_EINVAL, "st_play_linear: null argument");
+    if (n_w < 1) return fail(ST_EINVAL, "st_play_linear: n_w %lld < 1", (long long)n_w);
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_play_linear before st_seed + st_reset");
+    if (k <= 0) return ST_OK;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_play_linear: hipSetDevice(%d) failed", c->device);
+    // the ring: as many rows of one step's reward + done as fit 20 MiB, at most 32, at least one
+    const int64_t n = c->n;
+    const int64_t R = std::max<int64_t>(1, std::min<int64_t>(32, (int64_t(4) << 20) / n));
+    if (!c->play_buf) {
+        const hipError_t e = hipMalloc(&c->play_buf, (size_t)n * (size_t)(R * (sizeof(int32_t) + 1) + 1));
+        if (e != hipSuccess) {
+            c->play_buf = nullptr;
+            return fail(ST_ENOMEM, "st_play_linear: hipMalloc failed: %s", hipGetErrorString(e));
+        }
+    }
+    int32_t *ring_rew = c->play_buf;                                    // int32 [R][n]
+    uint8_t *act = reinterpret_cast<uint8_t *>(ring_rew + R * n);       // uint8 [n]
+    uint8_t *ring_done = act + n;                                       // uint8 [R][n]
+    const bool acc = d_return || d_episodes;
+    hipStream_t s = (hipStream_t)stream;
+    // With accumulators, step i writes its reward / done into the ring's next
+    // row, and one launch behind every R steps (and behind the last) adds the
+    // rows; the last of them also copies the last row out to d_reward / d_done.
+    // Without, the steps write d_reward / d_done themselves.  d_obs is the
+    // last step's alone.
+    int row = 0;
+    for (int64_t i = 0; i < k; ++i) {
+        const bool last = i == k - 1;
+        ST_HIP(st::launch_policy_linear(params(c), d_weights, n_w, nullptr, act, nullptr, nullptr, s));
+        int32_t *rew = acc || !d_reward ? ring_rew + (int64_t)row * n : d_reward;
+        uint8_t *done = acc || !d_done ? ring_done + (int64_t)row * n : d_done;
+        const int rc = step_impl(c, act, last ? d_obs : nullptr, nullptr, rew, done, stream, nullptr, nullptr,
+                                 /*gated=*/false);
+        if (rc != ST_OK) return rc;
+        if (!acc) continue;
+        if (++row == R || last) {
+            ST_HIP(st::launch_play_sum(params(c), ring_rew, ring_done, row, d_return, d_episodes,
+                                       last ? d_reward : nullptr, last ? d_done : nullptr, s));
+            row = 0;
+        }
+    }
     return ST_OK;
 }
 

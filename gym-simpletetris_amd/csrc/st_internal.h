@@ -93,6 +93,14 @@ hipError_t launch_policy_greedy(const KParams &p, uint64_t seed, int64_t t, uint
 // st_afterstates: feat int32 [n][ST_AFTER_NFEAT][S], boards uint32 [n][W][S] or null (S = 4 * (W + 6))
 hipError_t launch_afterstates(const KParams &p, int32_t *feat, uint32_t *boards, hipStream_t s);
 hipError_t launch_placement_actions(const KParams &p, const int32_t *slots, uint8_t *out, hipStream_t s);
+// st_policy_linear: weights float [n_w][ST_AFTER_NFEAT]; slots int32 [n], actions uint8 [n], scores
+// float [n], best int32 [ST_AFTER_NFEAT][n], any null
+hipError_t launch_policy_linear(const KParams &p, const float *weights, int64_t n_w, int32_t *slots, uint8_t *actions,
+                                float *scores, int32_t *best, hipStream_t s);
+// st_play_linear: adds rows 0 .. rows - 1 of reward int32 [rows][n] / done uint8 [rows][n] to acc_return
+// int64 [n] / acc_episodes int32 [n] (either null) and copies the last row to out_reward / out_done (either null)
+hipError_t launch_play_sum(const KParams &p, const int32_t *reward, const uint8_t *done, int rows, int64_t *acc_return,
+                           int32_t *acc_episodes, int32_t *out_reward, uint8_t *out_done, hipStream_t s);
 hipError_t launch_grayscale(const KParams &p, const uint32_t *obs, int size, int channels,
                             int as_u8, void *out, hipStream_t s);
 hipError_t launch_unwire(int W, int H, int64_t n_global, int shards, int64_t n_cap, const uint32_t *wire,

@@ -20,7 +20,8 @@
 // Three translation units are built from this file: the library's kernels (as
 // it is); with ST_STEP_EXPORT_TU defined (st_step_export.hip), k_step_export
 // and its launcher alone; with ST_AFTERSTATES_TU defined (st_afterstates.hip),
-// k_afterstates, k_placement_actions and their launchers alone.  step_logic /
+// k_afterstates, k_placement_actions, k_policy_linear, k_play_sum and their
+// launchers alone.  step_logic /
 // step_draw are shared source, but a second kernel instantiating them in ONE
 // module changes the code the compiler emits for k_step itself (it did: four
 // instructions around the lock ballot's LDS read); in a module of its own a
@@ -489,7 +490,9 @@ __device__ __forceinline__ LockRes lock_score(uint32_t kFlags, int32_t ncl, uint
 }
 
 // Every kernel below that exchanges data between lanes through LDS runs one
-// wave per workgroup.  LDS operations of a wavefront execute in order, so a
+// wave per workgroup, or (k_policy_linear: several envs per workgroup) gives
+// each wave an LDS slice of its own that no other wave touches, so the
+// exchange stays within one wave.  LDS operations of a wavefront execute in order, so a
 // read issued after another lane's write returns that write's data: the
 // exchange needs only compiler ordering, not __syncthreads' full
 // s_waitcnt lgkmcnt(0) (which would stall the wave for each LDS round trip).
@@ -3910,20 +3913,97 @@ __global__ __launch_bounds__(kWave) void k_policy_greedy(KParams p, uint64_t see
 // REWARD is lock_score's -- the rules of the step that locks the piece there
 // (:256-297) under the context's flags, from the env's holes and
 // piece_height counters.
+//
+// One slot's evaluation, shared by k_afterstates and k_policy_linear: the
+// collision test, the drop, the overlay, the clear, the column pass and
+// lock_score.  C: the wave's column words, column c at C[c] (c in [-P, W + P));
+// s: a slot in [0, S); f: the rows of st_after_feat as the slot has them if it
+// is valid (the caller masks the rows of an invalid one); col_out(c, w, valid):
+// column c of the board after the clear.  Returns the slot's validity.
+template <class ColOut>
+__device__ __forceinline__ bool eval_slot(const uint32_t *C, int W, int H, uint32_t flags, int id, int s,
+                                          int32_t old_holes, int32_t old_height, int32_t (&f)[ST_AFTER_NFEAT],
+                                          ColOut col_out) {
+    const uint32_t hmask = (1u << H) - 1u, floorb = ~hmask;
+    const int per = W + 6;
+    const int r = (s >= per) + (s >= 2 * per) + (s >= 3 * per), x = s - r * per - 3;
+    const uint32_t m = c_tab_m[id * 4 + r], g = c_tab_g[id * 4 + r];
+    const int x0 = box_x0(g, x);
+    uint32_t v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = C[x0 + j];
+    const bool valid = !collides_v(m, 0, v);
+    const int y = valid ? drop_box(g, 0, v) : 0;
+    bool above = false;
+    uint32_t pb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t byte = (m >> (8 * j)) & 0xFFu;
+        above = above || (byte != 0u && y + __builtin_ctz(byte) - 3 < 0);  // (a box column without cells)
+        pb[j] = pc_bits(m, j, y) & hmask;
+    }
+    // the board with the piece: column c gets the bits of the box column at c
+    uint32_t andv = hmask;
+    for (int c = 0; c < W; ++c) {
+        uint32_t w = C[c];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
+        andv &= w;
+    }
+    const int32_t ncl = __builtin_popcount(andv);
+    int32_t holes = 0, agg = 0, bump = 0, hprev = 0;
+    uint32_t orv = 0;
+    for (int c = 0; c < W; ++c) {
+        uint32_t w = C[c] & hmask;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
+        if (andv) w = compact(w, andv);
+        const int32_t h = H - (int32_t)__builtin_ctz(w | floorb);  // the column's height
+        holes += h - __builtin_popcount(w);
+        agg += h;
+        bump += c ? (h > hprev ? h - hprev : hprev - h) : 0;
+        hprev = h;
+        orv |= w;
+        col_out(c, w, valid);
+    }
+    int32_t rew = (flags & ST_REWARD_STEP) ? 1 : 0;  // :256
+    int32_t score = 0, lines = 0, nholes = 0, height = 0, deaths = 0;
+    lock_score<false>(flags, ncl, orv, [&] { return holes; }, old_holes, old_height, rew, score, lines, nholes, height,
+                      deaths);
+    f[ST_AFTER_VALID] = 1;
+    f[ST_AFTER_Y] = y;
+    f[ST_AFTER_LINES] = ncl;
+    f[ST_AFTER_HOLES] = holes;
+    f[ST_AFTER_HEIGHT] = orv ? H - (int32_t)__builtin_ctz(orv) : 0;
+    f[ST_AFTER_ROWS] = __builtin_popcount(orv);
+    f[ST_AFTER_ABOVE] = above ? 1 : 0;
+    f[ST_AFTER_DEAD] = (int32_t)(orv & 1u);
+    f[ST_AFTER_REWARD] = rew;
+    f[ST_AFTER_AGG_HEIGHT] = agg;
+    f[ST_AFTER_BUMPINESS] = bump;
+    return valid;
+}
+
+// The wave's W + 2 * P column words (floor bits, all-ones walls): lanes
+// 0 .. W + 2 * P - 1 write one word each.
+constexpr int kAfterP = 8;  // wall columns each side: the box's columns span [-6, W + 5]
+constexpr int kAfterCols = kMaxW + 2 * kAfterP;
+__device__ __forceinline__ void stage_env_columns(uint32_t *L, const KParams &p, int64_t e, int lane) {
+    if (lane < p.W + 2 * kAfterP) {
+        const int c = lane - kAfterP;
+        L[lane] = c >= 0 && c < p.W ? p.board[c * p.stride + e] | ~((1u << p.H) - 1u) : ~0u;
+    }
+}
+
 __global__ __launch_bounds__(kWave) void k_afterstates(KParams p, int32_t *__restrict__ feat,
                                                        uint32_t *__restrict__ boards) {
-    constexpr int P = 8;  // wall columns each side: the box's columns span [-6, W + 5]
-    __shared__ uint32_t L[kMaxW + 2 * P];
+    __shared__ uint32_t L[kAfterCols];
     const int lane = threadIdx.x;
     const int64_t e = blockIdx.x;  // the grid is p.n waves: padding envs are not evaluated
     const int64_t sd = p.stride;
     const int W = p.W, H = p.H;
-    const uint32_t hmask = (1u << H) - 1u, floorb = ~hmask;
-    const int per = W + 6, S = 4 * per;
-    if (lane < W + 2 * P) {
-        const int c = lane - P;
-        L[lane] = c >= 0 && c < W ? p.board[c * sd + e] | floorb : ~0u;
-    }
+    const int S = 4 * (W + 6);
+    stage_env_columns(L, p, e, lane);
     const uint32_t pid = p.piece[e] & 7u;
     const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
     const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
@@ -3934,64 +4014,14 @@ __global__ __launch_bounds__(kWave) void k_afterstates(KParams p, int32_t *__res
         const int s = s0 + lane;
         const bool live = s < S;
         const int sc = live ? s : S - 1;  // (lanes past the last slot compute it again, store nothing)
-        const int r = (sc >= per) + (sc >= 2 * per) + (sc >= 3 * per), x = sc - r * per - 3;
-        const uint32_t m = c_tab_m[id * 4 + r], g = c_tab_g[id * 4 + r];
-        const int x0 = box_x0(g, x);
-        uint32_t v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = L[x0 + j + P];
-        const bool valid = live && !collides_v(m, 0, v);
-        const int y = valid ? drop_box(g, 0, v) : 0;
-        bool above = false;
-        uint32_t pb[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t byte = (m >> (8 * j)) & 0xFFu;
-            above = above || (byte != 0u && y + __builtin_ctz(byte) - 3 < 0);  // (a box column without cells)
-            pb[j] = pc_bits(m, j, y) & hmask;
-        }
-        // the board with the piece: column c gets the bits of the box column at c
-        uint32_t andv = hmask;
-        for (int c = 0; c < W; ++c) {
-            uint32_t w = L[c + P];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
-            andv &= w;
-        }
-        const int32_t ncl = __builtin_popcount(andv);
-        int32_t holes = 0, agg = 0, bump = 0, hprev = 0;
-        uint32_t orv = 0;
-        for (int c = 0; c < W; ++c) {
-            uint32_t w = L[c + P] & hmask;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
-            if (andv) w = compact(w, andv);
-            const int32_t h = H - (int32_t)__builtin_ctz(w | floorb);  // the column's height
-            holes += h - __builtin_popcount(w);
-            agg += h;
-            bump += c ? (h > hprev ? h - hprev : hprev - h) : 0;
-            hprev = h;
-            orv |= w;
-            if (boards && live) boards[bbase + (size_t)c * S + s] = valid ? w : 0u;
-        }
-        int32_t rew = (p.flags & ST_REWARD_STEP) ? 1 : 0;  // :256
-        int32_t score = 0, lines = 0, nholes = 0, height = 0, deaths = 0;
-        lock_score<false>(p.flags, ncl, orv, [&] { return holes; }, old_holes, old_height, rew, score, lines, nholes,
-                          height, deaths);
+        int32_t f[ST_AFTER_NFEAT];
+        const bool valid = eval_slot(L + kAfterP, W, H, p.flags, id, sc, old_holes, old_height, f,
+                                     [&](int c, uint32_t w, bool ok) {
+                                         if (boards && live) boards[bbase + (size_t)c * S + s] = ok ? w : 0u;
+                                     });
         if (live) {
-            int32_t *f = feat + fbase + s;
-            auto put = [&](int row, int32_t val) { f[(size_t)row * S] = valid ? val : 0; };
-            put(ST_AFTER_VALID, 1);
-            put(ST_AFTER_Y, y);
-            put(ST_AFTER_LINES, ncl);
-            put(ST_AFTER_HOLES, holes);
-            put(ST_AFTER_HEIGHT, orv ? H - (int32_t)__builtin_ctz(orv) : 0);
-            put(ST_AFTER_ROWS, __builtin_popcount(orv));
-            put(ST_AFTER_ABOVE, above ? 1 : 0);
-            put(ST_AFTER_DEAD, (int32_t)(orv & 1u));
-            put(ST_AFTER_REWARD, rew);
-            put(ST_AFTER_AGG_HEIGHT, agg);
-            put(ST_AFTER_BUMPINESS, bump);
+#pragma unroll
+            for (int row = 0; row < ST_AFTER_NFEAT; ++row) feat[fbase + (size_t)row * S + s] = valid ? f[row] : 0;
         }
     }
 }
@@ -4014,6 +4044,177 @@ __global__ __launch_bounds__(256) void k_placement_actions(KParams p, const int3
         a = rot != trot ? 4u : (ax < tx ? 1u : (ax > tx ? 0u : 2u));
     }
     out[e] = (uint8_t)a;
+}
+
+// ---------------------------------------------------------------- linear feature player
+// st_policy_linear: env e scores every slot of its current piece with weight
+// row e % n_w and keeps the best one -- k_afterstates's evaluation (eval_slot)
+// without its output stream: per env 4 + 1 + 4 + 44 bytes leave the kernel.
+//
+// score = the float32 chain acc = acc + w[r] * (float)feat[r] over the rows
+// of st_after_feat in enum order from acc = 0, every product and every sum
+// rounded on its own.  No compiler flag can fuse the chain: lin_score passes
+// every product through an empty asm statement before it is added, so the
+// multiply and the add never meet in one expression the backend could
+// contract (-ffp-contract=fast on the command line included, which overrides
+// a `#pragma clang fp contract(off)`; __fmul_rn / __fadd_rn are plain * and +
+// in this toolchain's headers and would contract too).  The statement emits
+// no instruction.
+//
+// One wave per env, lane = slot, ceil(S / 64) passes; ST_POLICY_WAVES envs per
+// workgroup, each wave with its own W + 16 column words of LDS and no
+// workgroup barrier (a wave past the last env leaves at once).  A lane keeps
+// the first maximum of its own slots: the first pass sets it (10x20 has no
+// other), a later pass replaces it only on a strictly larger score, since a
+// lane's slots ascend.  Across lanes: the wave's maximum score over the lanes
+// that hold a candidate, then the lowest slot among the lanes that reach it --
+// two DPP reductions (wave_reduce), six VALU operations each, no LDS.  The lane
+// whose candidate won -- lane 0 if no slot is valid -- writes the env's
+// outputs with plain stores.
+//
+// st_play_linear's accumulators stay out of this kernel: its steps write
+// their reward / done into rows of a ring the context owns, and k_play_sum adds
+// a ring's worth at a time -- one lane per env, whole cache lines.  (Adding
+// in this kernel, one lane per wave or one wave per 64 envs, measured 3.8 /
+// 1.5 us per step at 65,536 envs.)
+__global__ __launch_bounds__(256) void k_play_sum(const int32_t *__restrict__ reward, const uint8_t *__restrict__ done,
+                                                  int rows, int64_t n, int64_t *__restrict__ ret,
+                                                  int32_t *__restrict__ episodes, int32_t *__restrict__ out_reward,
+                                                  uint8_t *__restrict__ out_done) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    int64_t r = 0;
+    int32_t d = 0;
+    for (int j = 0; j < rows; ++j) {
+        r += (int64_t)reward[(int64_t)j * n + e];
+        d += done[(int64_t)j * n + e] ? 1 : 0;
+    }
+    if (ret) ret[e] += r;
+    if (episodes) episodes[e] += d;
+    // the last row, i.e. the last step's outputs, for the caller
+    if (out_reward) out_reward[e] = reward[(int64_t)(rows - 1) * n + e];
+    if (out_done) out_done[e] = done[(int64_t)(rows - 1) * n + e];
+}
+
+__device__ __forceinline__ float lin_score(const float (&w)[ST_AFTER_NFEAT], const int32_t (&f)[ST_AFTER_NFEAT]) {
+#pragma clang fp contract(off)
+    float acc = 0.0f;
+#pragma unroll
+    for (int r = 0; r < ST_AFTER_NFEAT; ++r) {
+        float prod = w[r] * (float)f[r];
+        asm volatile("" : "+v"(prod));  // the rounded product, opaque to the add below
+        acc = acc + prod;
+    }
+    return acc;
+}
+
+// op over the 64 lanes of a wave whose lanes are all active, in every lane:
+// within each row of 16 by quad permutes and row rotations, then row_bcast:15
+// into rows 1 and 3 and row_bcast:31 into rows 2 and 3 (gfx9 DPP), which leaves
+// the result in lane 63.  A lane the controls do not write keeps its own value
+// (old = x), and op(x, x) = x for the max / min this is used with.
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ int dpp_from(int x) {
+    return __builtin_amdgcn_update_dpp(x, x, CTRL, ROW_MASK, 0xF, false);
+}
+template <class Op>
+__device__ __forceinline__ int wave_reduce(int x, Op op) {
+    x = op(x, dpp_from<0xB1>(x));         // quad_perm:[1,0,3,2]
+    x = op(x, dpp_from<0x4E>(x));         // quad_perm:[2,3,0,1]
+    x = op(x, dpp_from<0x124>(x));        // row_ror:4
+    x = op(x, dpp_from<0x128>(x));        // row_ror:8
+    x = op(x, dpp_from<0x142, 0xA>(x));   // row_bcast:15 into rows 1, 3
+    x = op(x, dpp_from<0x143, 0xC>(x));   // row_bcast:31 into rows 2, 3
+    return __builtin_amdgcn_readlane(x, kWave - 1);
+}
+
+template <bool FIRST>
+struct PassTag {
+    static constexpr bool value = FIRST;
+};
+
+#ifndef ST_POLICY_WAVES
+#define ST_POLICY_WAVES 4  // envs (waves) per workgroup: the block-shape A/B, DESIGN "Linear feature player"
+#endif
+
+template <int WAVES>
+__global__ __launch_bounds__(WAVES *kWave) void k_policy_linear(KParams p, const float *__restrict__ wts, int64_t n_w,
+                                                                int32_t *__restrict__ slots,
+                                                                uint8_t *__restrict__ actions,
+                                                                float *__restrict__ scores,
+                                                                int32_t *__restrict__ best) {
+    __shared__ uint32_t Lall[WAVES * kAfterCols];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t e = (int64_t)blockIdx.x * WAVES + wave;
+    if (e >= p.n) return;  // (wave-uniform; the kernel has no workgroup barrier)
+    uint32_t *L = Lall + wave * kAfterCols;
+    const int64_t sd = p.stride;
+    const int W = p.W, H = p.H;
+    const int per = W + 6, S = 4 * per;
+    stage_env_columns(L, p, e, lane);
+    const uint32_t pw = p.piece[e];
+    const uint32_t pid = pw & 7u;
+    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
+    const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
+    const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd + e];
+    // e < 2^24 (st_create), so the row index is 32-bit arithmetic
+    const uint32_t wrow = n_w > e ? (uint32_t)e : (uint32_t)e % (uint32_t)n_w;
+    float w[ST_AFTER_NFEAT];
+#pragma unroll
+    for (int r = 0; r < ST_AFTER_NFEAT; ++r) w[r] = wts[(size_t)wrow * ST_AFTER_NFEAT + r];
+    wave_sync();
+    // the lane's candidate: its best slot so far (-1: none), that slot's score and rows
+    int32_t bslot;
+    float bscore;
+    int32_t bf[ST_AFTER_NFEAT];
+    auto pass = [&](int s0, auto first) {
+        const int s = s0 + lane;
+        const bool live = s < S;
+        int32_t f[ST_AFTER_NFEAT];
+        const bool valid = eval_slot(L + kAfterP, W, H, p.flags, id, live ? s : S - 1, old_holes, old_height, f,
+                                     [](int, uint32_t, bool) {});
+        const float sc = lin_score(w, f);
+        if constexpr (decltype(first)::value) {  // (score and rows are read only where bslot >= 0)
+            bslot = live && valid ? s : -1;
+            bscore = sc;
+#pragma unroll
+            for (int r = 0; r < ST_AFTER_NFEAT; ++r) bf[r] = f[r];
+        } else if (live && valid && (bslot < 0 || sc > bscore)) {
+            bslot = s;
+            bscore = sc;
+#pragma unroll
+            for (int r = 0; r < ST_AFTER_NFEAT; ++r) bf[r] = f[r];
+        }
+    };
+    pass(0, PassTag<true>{});
+    for (int s0 = kWave; s0 < S; s0 += kWave) pass(s0, PassTag<false>{});
+    // the wave's maximum over the candidates, then the lowest slot that reaches
+    // it.  With finite weights some candidate equals the maximum; a NaN score
+    // equals nothing, and then every candidate counts as reaching it, so that
+    // the slot stays a valid one.
+    const bool has = bslot >= 0;
+    const float top = __int_as_float(wave_reduce(__float_as_int(has ? bscore : -__builtin_inff()), [](int a, int b) {
+        return __float_as_int(__builtin_fmaxf(__int_as_float(a), __int_as_float(b)));
+    }));
+    bool tied = has && bscore == top;
+    if (__ballot(tied) == 0) tied = has;
+    const int32_t win = wave_reduce(tied ? bslot : INT32_MAX, [](int a, int b) { return a < b ? a : b; });
+    const bool none = win == INT32_MAX;  // no valid slot: lane 0 writes slot -1, action 2, score 0, zero rows
+    if (none ? lane == 0 : tied && bslot == win) {
+        if (slots) slots[e] = none ? -1 : win;
+        if (scores) scores[e] = none ? 0.0f : bscore;
+        if (actions) {
+            const int rot = (int)((pw >> 3) & 3u), ax = (int)((pw >> 5) & 63u);
+            const int trot = (win >= per) + (win >= 2 * per) + (win >= 3 * per), tx = win - trot * per - 3;
+            // k_placement_actions's rule
+            actions[e] = (uint8_t)(none ? 2u : rot != trot ? 4u : (ax < tx ? 1u : (ax > tx ? 0u : 2u)));
+        }
+        if (best) {
+#pragma unroll
+            for (int r = 0; r < ST_AFTER_NFEAT; ++r) best[(size_t)r * p.n + e] = none ? 0 : bf[r];
+        }
+    }
 }
 #endif  // ST_AFTERSTATES_TU
 
@@ -4043,6 +4244,21 @@ hipError_t launch_afterstates(const KParams &p, int32_t *feat, uint32_t *boards,
 
 hipError_t launch_placement_actions(const KParams &p, const int32_t *slots, uint8_t *out, hipStream_t s) {
     hipLaunchKernelGGL(k_placement_actions, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p, slots, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_linear(const KParams &p, const float *weights, int64_t n_w, int32_t *slots, uint8_t *actions,
+                                float *scores, int32_t *best, hipStream_t s) {
+    constexpr int WV = ST_POLICY_WAVES;
+    hipLaunchKernelGGL((k_policy_linear<WV>), dim3((unsigned)((p.n + WV - 1) / WV)), dim3(WV * kWave), 0, s, p, weights,
+                       n_w, slots, actions, scores, best);
+    return hipGetLastError();
+}
+
+hipError_t launch_play_sum(const KParams &p, const int32_t *reward, const uint8_t *done, int rows, int64_t *acc_return,
+                           int32_t *acc_episodes, int32_t *out_reward, uint8_t *out_done, hipStream_t s) {
+    hipLaunchKernelGGL(k_play_sum, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, reward, done, rows, p.n,
+                       acc_return, acc_episodes, out_reward, out_done);
     return hipGetLastError();
 }
 #else  // the library's own translation unit

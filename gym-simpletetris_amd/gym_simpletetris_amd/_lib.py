@@ -107,6 +107,8 @@ SIG = {
     "st_after_slots": ([_i32], ctypes.c_int),
     "st_afterstates": ([_vp, _vp, _vp, _vp], ctypes.c_int),
     "st_placement_actions": ([_vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_policy_linear": ([_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_play_linear": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_debug_stamps": ([_vp, _vp, _i64], ctypes.c_int),
     "st_last_error": ([], ctypes.c_char_p),
     "st_abi_version": ([], ctypes.c_int),
@@ -140,7 +142,8 @@ def load(path: str = LIB_PATH):
         if not hasattr(L, name):
             if ab_override:
                 continue
-            # an addition that did not change the ABI number (st_step_export, st_afterstates):
+            # an addition that did not change the ABI number (st_step_export, st_afterstates,
+            # st_policy_linear):
             # the library on disk was built before it
             raise ImportError(f"{path}: no symbol {name} (a stale build of ABI {abi}: rebuild it with "
                               "`make -C gym-simpletetris_amd/csrc`)")

@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import ctypes
 import os
+from collections.abc import Mapping
+from types import MappingProxyType
 from typing import Optional, Sequence
 
 import numpy as np
@@ -172,6 +174,63 @@ class Afterstates:
         if row is None:
             raise AttributeError(name)
         return self.feat[:, row]
+
+
+# st_policy_greedy's score as linear feature weights: 80 * lines - 12 * holes
+# - 3 * height - 2000 * above (rows by their names in _lib.AFTER)
+GREEDY_WEIGHTS = MappingProxyType(dict(lines=80.0, holes=-12.0, height=-3.0, above=-2000.0))
+
+
+def weight_rows(weights) -> np.ndarray:
+    """Host weights for policy_linear / play_linear as float32 [n_w, AFTER_NFEAT]:
+    a mapping by _lib.AFTER name (missing names are 0; the header's enum order
+    places the values), a sequence of AFTER_NFEAT numbers, or a sequence of
+    such mappings / sequences (one row per candidate)."""
+    def row(w):
+        if isinstance(w, Mapping):
+            unknown = sorted(set(w) - set(C.AFTER))
+            if unknown:
+                raise ValueError(f"weights: no feature row named {unknown[0]!r} (rows: {', '.join(C.AFTER)})")
+            v = np.zeros(C.AFTER_NFEAT, np.float32)
+            for name, val in w.items():
+                v[C.AFTER[name]] = val
+            return v
+        w = np.asarray(w)
+        if w.shape != (C.AFTER_NFEAT,):
+            raise ValueError(f"weights: a row needs {C.AFTER_NFEAT} values, got shape {w.shape}")
+        return w
+    if isinstance(weights, Mapping):
+        out = row(weights)
+    elif isinstance(weights, (list, tuple)) and any(isinstance(w, Mapping) for w in weights):
+        out = np.stack([row(w) for w in weights])
+    elif isinstance(weights, (list, tuple, np.ndarray)):
+        out = np.asarray(weights)
+    else:
+        raise TypeError(f"weights: need a tensor, a sequence or a mapping by feature name, got {type(weights)}")
+    if out.dtype.kind not in "fiu":
+        raise TypeError(f"weights must be real numbers, got {out.dtype}")
+    out = out.astype(np.float32)
+    out = out[None] if out.ndim == 1 else out
+    if out.ndim != 2 or out.shape[1] != C.AFTER_NFEAT or out.shape[0] < 1:
+        raise ValueError(f"weights: need [{C.AFTER_NFEAT}] or [n_w, {C.AFTER_NFEAT}] values, got shape {np.shape(weights)}")
+    return np.ascontiguousarray(out)
+
+
+class LinearChoice:
+    """TetrisBatch.policy_linear()'s result: `slots` int32 [n] (-1: no valid
+    slot), `actions` uint8 [n] (as step() takes them), `scores` float32 [n] and
+    `feat` int32 [AFTER_NFEAT, n], the chosen slot's feature rows with the env
+    innermost; every row by its name in _lib.AFTER as an [n] view of feat
+    (.lines, .holes, ...).  A field not asked for (`out`) is None."""
+
+    def __init__(self, slots, actions, scores, feat):
+        self.slots, self.actions, self.scores, self.feat = slots, actions, scores, feat
+
+    def __getattr__(self, name):  # (only names not found otherwise)
+        row = C.AFTER.get(name)
+        if row is None or self.feat is None:
+            raise AttributeError(name)
+        return self.feat[row]
 
 
 class TetrisBatch:
@@ -734,6 +793,91 @@ class TetrisBatch:
             _check_tensor(out, "out", (self.n,), (torch.uint8,), self.device)
         C.check(self._L.st_placement_actions(self._ctx, _ptr(s), _ptr(out), self._stream()))
         return out
+
+    # ------------------------------------------------------------ linear feature players
+    def _weights(self, weights) -> torch.Tensor:
+        """policy_linear's / play_linear's weights as a float32 device tensor
+        [n_w, AFTER_NFEAT]: a device tensor [AFTER_NFEAT] or [n_w, AFTER_NFEAT]
+        as it is (checked, never converted), anything else through weight_rows."""
+        if isinstance(weights, torch.Tensor):
+            w = weights[None] if weights.dim() == 1 else weights
+            _check_tensor(w, "weights", (None, C.AFTER_NFEAT), (torch.float32,), self.device)
+            if w.shape[0] < 1:
+                raise ValueError("weights: no rows")
+            return w
+        return torch.as_tensor(weight_rows(weights), device=self.device)
+
+    def policy_linear(self, weights, out=None) -> LinearChoice:
+        """Every env's best placement under linear feature weights, in one
+        launch (st_policy_linear).  Env e scores every placement slot of its
+        current piece -- afterstates()'s slots and feature rows -- with weight
+        row e % n_w: float32 acc = acc + w[r] * feat[r] over the rows in
+        _lib.AFTER order from 0, each product and sum rounded on its own; the
+        valid slot with the largest score wins, ties to the lowest slot.
+        weights: a float32 device tensor [AFTER_NFEAT] or [n_w, AFTER_NFEAT]
+        (one row per candidate of a population), a host sequence of that
+        shape, or a dict by feature name (GREEDY_WEIGHTS; missing names are 0;
+        'valid' is a bias).  Returns a LinearChoice: .slots (-1 where no slot
+        is valid: then action 2, score 0, feature column 0), .actions (what
+        placement_actions gives for the slot), .scores, .feat [AFTER_NFEAT, n]
+        and its rows by name.  Reads the state, changes none of it.
+        `out`: a (slots, actions, scores, feat) tuple of device tensors to
+        write; None entries are not computed (at least one must be given)."""
+        n = self.n
+        w = self._weights(weights)
+        if out is None:
+            out = (torch.empty(n, dtype=torch.int32, device=self.device),
+                   torch.empty(n, dtype=torch.uint8, device=self.device),
+                   torch.empty(n, dtype=torch.float32, device=self.device),
+                   torch.empty((C.AFTER_NFEAT, n), dtype=torch.int32, device=self.device))
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 4:
+                raise ValueError("out: a (slots, actions, scores, feat) tuple, None for an output not wanted")
+            if all(t is None for t in out):
+                raise ValueError("out: at least one output tensor is needed")
+            for t, name, shape, dt in zip(out, ("slots", "actions", "scores", "feat"),
+                                          ((n,), (n,), (n,), (C.AFTER_NFEAT, n)),
+                                          (torch.int32, torch.uint8, torch.float32, torch.int32)):
+                if t is not None:
+                    _check_tensor(t, "out " + name, shape, (dt,), self.device)
+        sl, ac, sc, ft = out
+        C.check(self._L.st_policy_linear(self._ctx, _ptr(w), w.shape[0], _ptr(sl), _ptr(ac), _ptr(sc), _ptr(ft),
+                                         self._stream()))
+        return LinearChoice(sl, ac, sc, ft)
+
+    def play_linear(self, weights, k: int, returns: Optional[torch.Tensor] = None,
+                    episodes: Optional[torch.Tensor] = None, obs: str = "none"):
+        """k steps of policy_linear(weights) -> step, enqueued by ONE library
+        call (st_play_linear: no Python, no host read-back between the steps),
+        identical to k rounds of policy_linear + step by hand.  Adds every
+        step's reward to `returns` (int64 [n]) and every step's done to
+        `episodes` (int32 [n]) -- device tensors that are continued where the
+        caller left them, or fresh zeros -- and returns (returns, episodes).
+        With one weight row per candidate and autoreset='same_step' that is a
+        CEM / ES generation in one call and one read-back; under
+        autoreset='none' a dead env keeps being stepped in the state the
+        reference leaves, as the loop by hand would.  The last step's outputs
+        are in .reward, .done and (obs='packed') .obs.  Not gated, never
+        raises for actions (the policy's are 0..6); k = 0 does nothing.  The
+        library keeps the actions and the rows it sums in one buffer per
+        batch: keep a batch's play_linear calls on one stream."""
+        if obs not in ("packed", "none"):
+            raise ValueError("obs must be 'packed' or 'none'")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+            raise ValueError(f"k must be an integer >= 0, got {k!r}")
+        w = self._weights(weights)
+        if returns is None:
+            returns = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        else:
+            _check_tensor(returns, "returns", (self.n,), (torch.int64,), self.device)
+        if episodes is None:
+            episodes = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        else:
+            _check_tensor(episodes, "episodes", (self.n,), (torch.int32,), self.device)
+        C.check(self._L.st_play_linear(self._ctx, _ptr(w), w.shape[0], int(k), _ptr(returns), _ptr(episodes),
+                                       _ptr(self.obs) if obs == "packed" else None, _ptr(self.reward),
+                                       _ptr(self.done), self._stream()))
+        return returns, episodes
 
 
 def unwire(wire: torch.Tensor, width: int, height: int):

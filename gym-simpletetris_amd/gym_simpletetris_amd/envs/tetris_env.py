@@ -546,6 +546,19 @@ class TetrisVecEnv:
         uint8 actions step() takes, toward the chosen placement slots."""
         return self.engine.placement_actions(slots, out=out)
 
+    def policy_linear(self, weights, out=None):
+        """TetrisBatch.policy_linear of the engine, on its stream: every env's
+        best placement under linear feature weights (slot, action, score and
+        feature row) in one launch."""
+        return self.engine.policy_linear(weights, out=out)
+
+    def play_linear(self, weights, k, returns=None, episodes=None, obs="none"):
+        """TetrisBatch.play_linear of the engine: k steps of policy_linear ->
+        step in one library call, straight on the engine (no info, no
+        final_observation: with autoreset a finished env simply plays on);
+        returns the (returns, episodes) accumulators."""
+        return self.engine.play_linear(weights, k, returns=returns, episodes=episodes, obs=obs)
+
     def close(self):
         self._pool.clear()
         self.engine.close()

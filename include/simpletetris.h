@@ -36,7 +36,8 @@ extern "C" {
  * st_stream_wait (additions only).  4: st_step_n (addition only).
  * st_step_export: addition only, version unchanged (a build without it is
  * refused by the host package when it binds the symbol); so are
- * st_after_slots / st_afterstates / st_placement_actions.
+ * st_after_slots / st_afterstates / st_placement_actions and
+ * st_policy_linear / st_play_linear.
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -380,6 +381,70 @@ int st_afterstates(st_ctx *ctx, int32_t *d_feat, uint32_t *d_boards, st_stream s
  * st_placement_actions -> st_step, repeated, plays the chosen placement out.
  * NULL checks and ST_ESTATE as for st_afterstates. */
 int st_placement_actions(st_ctx *ctx, const int32_t *d_slots, uint8_t *d_actions, st_stream stream);
+
+/* Linear feature player (Dellacherie / BCTS players, CEM or ES over feature
+ * weights): env e scores every placement slot of its current piece with
+ * weight row e % n_w and picks one, in one launch.
+ * d_weights: float32 [n_w][ST_AFTER_NFEAT] on the device, n_w >= 1 (one row
+ * for every env, or one row per candidate of a population).
+ *
+ * Slots, validity and the eleven feature values of a slot are st_afterstates's,
+ * word for word: the same board, the same piece id, the same scoring flags
+ * and the same holes / piece_height counters.
+ *
+ * Score of a slot, in float32, every product and every sum rounded on its own
+ * (no fused multiply-add):
+ *   acc = 0.0f;
+ *   for r = 0 .. ST_AFTER_NFEAT - 1, in enum order: acc = acc + w[r] * (float)feat[r];
+ * Every feature is an integer far below 2^24, so its conversion is exact.  Row
+ * VALID is 1 on every candidate: its weight is a bias.
+ *
+ * Choice: the valid slot with the largest score; ties go to the lowest slot
+ * number (st_policy_greedy's "first maximum in rotation, then x order").  If
+ * no slot is valid: slot -1, score 0.0f, and the d_best column all zero.
+ * Weights must be finite; with others the result is unspecified, except that
+ * the slot stays in [-1, S) and nothing faults.
+ *
+ * d_slots   int32 [n_envs] or NULL: the chosen slot.
+ * d_actions uint8 [n_envs] or NULL: st_placement_actions's rule for the chosen
+ *           slot and the live piece (4, else 1 or 0, else 2); 2 for slot -1.
+ * d_scores  float [n_envs] or NULL: the chosen slot's score.
+ * d_best    int32 [ST_AFTER_NFEAT][n_envs] or NULL: row r of the chosen slot at
+ *           [r][e], the env innermost (what a TD learner on afterstate
+ *           features stores).
+ * Like st_afterstates it reads the state enqueued before it on `stream` and
+ * changes none of it, needs no st_mt_sync, is not gated and consumes no gate.
+ * ST_EINVAL for a NULL ctx, NULL d_weights, n_w < 1 or all four outputs NULL;
+ * ST_ESTATE before st_seed + st_reset; both before any GPU call. */
+int st_policy_linear(st_ctx *ctx, const float *d_weights, int64_t n_w,
+                     int32_t *d_slots, uint8_t *d_actions, float *d_scores, int32_t *d_best,
+                     st_stream stream);
+
+/* k times (st_policy_linear -> st_step), enqueued by one host call: iteration
+ * i writes the policy's actions into a buffer the context owns (allocated on
+ * the first call, freed by st_destroy) and runs the ordinary step on them.
+ * d_return   int64 [n_envs] or NULL: += the reward of every one of the k steps.
+ * d_episodes int32 [n_envs] or NULL: += the done of every one of the k steps.
+ *   Both add to what the caller left in them, so consecutive calls chain
+ *   (zero them before the first).
+ * d_obs / d_reward / d_done: the LAST step's outputs as st_step writes them
+ *   (as with st_step_n), any of them NULL.
+ * That buffer (the actions, and the rows of reward / done the sums are taken
+ * from) is one per context: calls on the same context must be ordered on one
+ * stream, or the later one enqueued only after the earlier has finished; two
+ * calls in flight on different streams would overwrite each other's rows.
+ * The steps are not gated and an armed st_gate_actions stays armed; the
+ * st_set_action_flag word is honoured as in st_step.  k <= 0 does nothing.
+ * Works under both autoreset modes: under ST_AUTORESET_SAME_STEP a finished
+ * env starts its next episode in the step that ended it (what evaluating a
+ * population wants); under ST_AUTORESET_NONE a dead env keeps being stepped
+ * in the state the reference leaves behind, exactly as k calls of
+ * st_policy_linear + st_step by hand would.
+ * ST_EINVAL for a NULL ctx, NULL d_weights or n_w < 1, ST_ESTATE before
+ * st_seed + st_reset, both before any GPU call. */
+int st_play_linear(st_ctx *ctx, const float *d_weights, int64_t n_w, int64_t k,
+                   int64_t *d_return, int32_t *d_episodes,
+                   uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
 
 /* Synthetic action source used by the benchmark and the parity tests:
  * d_out[e] = splitmix64(seed ^ ((t << 32) ^ (global_offset + e))) % 7. */
