@@ -36,9 +36,10 @@ struct st_ctx {
     uint32_t gate_epoch;
     bool gate_armed;
     bool gate_pending;
-    // st_play_linear: one allocation made on first use -- a ring of reward
-    // rows int32 [R][n], the policy's actions uint8 [n], a ring of done rows
-    // uint8 [R][n]
+    // st_play_linear / st_step_placements / st_play_linear_placements: one
+    // allocation made on first use (play_parts) -- a ring of reward rows int32
+    // [R][n], the policy's actions uint8 [n], a ring of done rows uint8 [R][n],
+    // the constant action 2 (hard drop) uint8 [n], filled then
     int32_t *play_buf;
 };
 
@@ -113,6 +114,42 @@ void free_state(st_ctx *c) {
     c->stamps = nullptr;
     c->board = c->piece = c->mt = nullptr;
     c->stats = nullptr;
+}
+
+// The parts of the context's play buffer, allocated (and its constant row
+// filled, on `s`, waited for) on first use; freed by free_state.
+struct PlayParts {
+    int64_t R;           // ring rows: one step's reward + done each, as many as fit 20 MiB, at most 32, at least one
+    int32_t *ring_rew;   // int32 [R][n]
+    uint8_t *act;        // uint8 [n]
+    uint8_t *ring_done;  // uint8 [R][n]
+    uint8_t *twos;       // uint8 [n], every byte 2
+};
+
+int play_parts(st_ctx *c, const char *fn, hipStream_t s, PlayParts *out) {
+    const int64_t n = c->n;
+    const int64_t R = std::max<int64_t>(1, std::min<int64_t>(32, (int64_t(4) << 20) / n));
+    PlayParts q;
+    q.R = R;
+    if (!c->play_buf) {
+        int32_t *buf = nullptr;
+        hipError_t e = hipMalloc(&buf, (size_t)n * (size_t)(R * (sizeof(int32_t) + 1) + 2));
+        if (e != hipSuccess) return fail(ST_ENOMEM, "%s: hipMalloc failed: %s", fn, hipGetErrorString(e));
+        uint8_t *twos = reinterpret_cast<uint8_t *>(buf + R * n) + n + R * n;
+        e = hipMemsetAsync(twos, 2, (size_t)n, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hipFree(buf);
+            return fail(ST_EHIP, "%s: filling the hard-drop actions: %s", fn, hipGetErrorString(e));
+        }
+        c->play_buf = buf;
+    }
+    q.ring_rew = c->play_buf;
+    q.act = reinterpret_cast<uint8_t *>(q.ring_rew + R * n);
+    q.ring_done = q.act + n;
+    q.twos = q.ring_done + R * n;
+    *out = q;
+    return ST_OK;
 }
 
 }  // namespace
@@ -569,29 +606,23 @@ int st_policy_linear(st_ctx *c, const float *d_weights, int64_t n_w, int32_t *d_
     return ST_OK;
 }
 
-int st_play_linear(st_ctx *c, const float *d_weights, int64_t n_w, int64_t k, int64_t *d_return, int32_t *d_episodes,
-                   uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream) {
-    if (!c || !d_weights) return fail(ST_EINVAL, "st_play_linear: null argument");
-    if (n_w < 1) return fail(ST_EINVAL, "st_play_linear: n_w %lld < 1", (long long)n_w);
-    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_play_linear before st_seed + st_reset");
+// st_play_linear (commit false: the policy's primitive action, then the step
+// on it) and st_play_linear_placements (commit true: the policy commits its
+// slot, then the step on the constant hard drop)
+static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weights, int64_t n_w, int64_t k,
+                     int64_t *d_return, int32_t *d_episodes, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
+                     st_stream stream) {
+    if (!c || !d_weights) return fail(ST_EINVAL, "%s: null argument", fn);
+    if (n_w < 1) return fail(ST_EINVAL, "%s: n_w %lld < 1", fn, (long long)n_w);
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "%s before st_seed + st_reset", fn);
     if (k <= 0) return ST_OK;
     DeviceGuard g(c->device);
-    if (!g.ok) return fail(ST_EHIP, "st_play_linear: hipSetDevice(%d) failed", c->device);
-    // the ring: as many rows of one step's reward + done as fit 20 MiB, at most 32, at least one
-    const int64_t n = c->n;
-    const int64_t R = std::max<int64_t>(1, std::min<int64_t>(32, (int64_t(4) << 20) / n));
-    if (!c->play_buf) {
-        const hipError_t e = hipMalloc(&c->play_buf, (size_t)n * (size_t)(R * (sizeof(int32_t) + 1) + 1));
-        if (e != hipSuccess) {
-            c->play_buf = nullptr;
-            return fail(ST_ENOMEM, "st_play_linear: hipMalloc failed: %s", hipGetErrorString(e));
-        }
-    }
-    int32_t *ring_rew = c->play_buf;                                    // int32 [R][n]
-    uint8_t *act = reinterpret_cast<uint8_t *>(ring_rew + R * n);       // uint8 [n]
-    uint8_t *ring_done = act + n;                                       // uint8 [R][n]
-    const bool acc = d_return || d_episodes;
+    if (!g.ok) return fail(ST_EHIP, "%s: hipSetDevice(%d) failed", fn, c->device);
     hipStream_t s = (hipStream_t)stream;
+    PlayParts q;
+    if (const int rc = play_parts(c, fn, s, &q)) return rc;
+    const int64_t n = c->n, R = q.R;
+    const bool acc = d_return || d_episodes;
     // With accumulators, step i writes its reward / done into the ring's next
     // row, and one launch behind every R steps (and behind the last) adds the
     // rows; the last of them also copies the last row out to d_reward / d_done.
@@ -600,20 +631,57 @@ int st_play_linear(st_ctx *c, const float *d_weights, int64_t n_w, int64_t k, in
     int row = 0;
     for (int64_t i = 0; i < k; ++i) {
         const bool last = i == k - 1;
-        ST_HIP(st::launch_policy_linear(params(c), d_weights, n_w, nullptr, act, nullptr, nullptr, s));
-        int32_t *rew = acc || !d_reward ? ring_rew + (int64_t)row * n : d_reward;
-        uint8_t *done = acc || !d_done ? ring_done + (int64_t)row * n : d_done;
-        const int rc = step_impl(c, act, last ? d_obs : nullptr, nullptr, rew, done, stream, nullptr, nullptr,
-                                 /*gated=*/false);
+        if (commit) ST_HIP(st::launch_policy_linear_commit(params(c), d_weights, n_w, s));
+        else ST_HIP(st::launch_policy_linear(params(c), d_weights, n_w, nullptr, q.act, nullptr, nullptr, s));
+        int32_t *rew = acc || !d_reward ? q.ring_rew + (int64_t)row * n : d_reward;
+        uint8_t *done = acc || !d_done ? q.ring_done + (int64_t)row * n : d_done;
+        const int rc = step_impl(c, commit ? q.twos : q.act, last ? d_obs : nullptr, nullptr, rew, done, stream,
+                                 nullptr, nullptr, /*gated=*/false);
         if (rc != ST_OK) return rc;
         if (!acc) continue;
         if (++row == R || last) {
-            ST_HIP(st::launch_play_sum(params(c), ring_rew, ring_done, row, d_return, d_episodes,
+            ST_HIP(st::launch_play_sum(params(c), q.ring_rew, q.ring_done, row, d_return, d_episodes,
                                        last ? d_reward : nullptr, last ? d_done : nullptr, s));
             row = 0;
         }
     }
     return ST_OK;
+}
+
+int st_play_linear(st_ctx *c, const float *d_weights, int64_t n_w, int64_t k, int64_t *d_return, int32_t *d_episodes,
+                   uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream) {
+    return play_impl(c, "st_play_linear", false, d_weights, n_w, k, d_return, d_episodes, d_obs, d_reward, d_done,
+                     stream);
+}
+
+int st_play_linear_placements(st_ctx *c, const float *d_weights, int64_t n_w, int64_t k, int64_t *d_return,
+                              int32_t *d_episodes, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
+                              st_stream stream) {
+    return play_impl(c, "st_play_linear_placements", true, d_weights, n_w, k, d_return, d_episodes, d_obs, d_reward,
+                     d_done, stream);
+}
+
+int st_place(st_ctx *c, const int32_t *d_slots, uint8_t *d_placed, st_stream stream) {
+    if (!c || !d_slots) return fail(ST_EINVAL, "st_place: null argument");
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_place before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_place: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_place(params(c), d_slots, d_placed, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_step_placements(st_ctx *c, const int32_t *d_slots, uint8_t *d_placed, uint32_t *d_obs, int32_t *d_reward,
+                       uint8_t *d_done, st_stream stream) {
+    if (!c || !d_slots) return fail(ST_EINVAL, "st_step_placements: null argument");
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_step_placements before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_step_placements: hipSetDevice(%d) failed", c->device);
+    hipStream_t s = (hipStream_t)stream;
+    PlayParts q;
+    if (const int rc = play_parts(c, "st_step_placements", s, &q)) return rc;
+    ST_HIP(st::launch_place(params(c), d_slots, d_placed, s));
+    // (not gated: the actions are the context's own, an armed st_gate_actions stays armed)
+    return step_impl(c, q.twos, d_obs, nullptr, d_reward, d_done, stream, nullptr, nullptr, /*gated=*/false);
 }
 
 int st_check_actions(const uint8_t *d_actions, int64_t n, uint32_t *d_flag, st_stream stream) {

@@ -97,6 +97,10 @@ hipError_t launch_placement_actions(const KParams &p, const int32_t *slots, uint
 // float [n], best int32 [ST_AFTER_NFEAT][n], any null
 hipError_t launch_policy_linear(const KParams &p, const float *weights, int64_t n_w, int32_t *slots, uint8_t *actions,
                                 float *scores, int32_t *best, hipStream_t s);
+// st_place: commits slots int32 [n] (the piece row alone is written); placed uint8 [n] or null
+hipError_t launch_place(const KParams &p, const int32_t *slots, uint8_t *placed, hipStream_t s);
+// st_play_linear_placements: st_policy_linear's choice, committed like launch_place; no other output
+hipError_t launch_policy_linear_commit(const KParams &p, const float *weights, int64_t n_w, hipStream_t s);
 // st_play_linear: adds rows 0 .. rows - 1 of reward int32 [rows][n] / done uint8 [rows][n] to acc_return
 // int64 [n] / acc_episodes int32 [n] (either null) and copies the last row to out_reward / out_done (either null)
 hipError_t launch_play_sum(const KParams &p, const int32_t *reward, const uint8_t *done, int rows, int64_t *acc_return,

@@ -20,8 +20,8 @@
 // Three translation units are built from this file: the library's kernels (as
 // it is); with ST_STEP_EXPORT_TU defined (st_step_export.hip), k_step_export
 // and its launcher alone; with ST_AFTERSTATES_TU defined (st_afterstates.hip),
-// k_afterstates, k_placement_actions, k_policy_linear, k_play_sum and their
-// launchers alone.  step_logic /
+// k_afterstates, k_placement_actions, k_place, k_policy_linear, k_play_sum and
+// their launchers alone.  step_logic /
 // step_draw are shared source, but a second kernel instantiating them in ONE
 // module changes the code the compiler emits for k_step itself (it did: four
 // instructions around the lock ballot's LDS read); in a module of its own a
@@ -4046,6 +4046,50 @@ __global__ __launch_bounds__(256) void k_placement_actions(KParams p, const int3
     out[e] = (uint8_t)a;
 }
 
+// ---------------------------------------------------------------- placement step
+// st_place: commit slot slots[e] of env e (simpletetris.h, "Placement step").
+// A VALID slot -- in [0, S) and not is_occupied(cells, (x, 0), board), the
+// validity of eval_slot on the env's current board and piece id -- makes the
+// env's piece the slot's: rotation rot, anchor (x, 0) and a lock counter of
+// lock_mod - 1 = max(lock_delay, 0), from which the next drop's
+// (x + 1) % lock_mod is 0 (tetris_env.py:175): the hard drop behind it locks
+// the piece whatever lock_delay is.  Any other slot leaves the piece word as
+// it is, lock counter included.  Board, counters, MT and preview are not
+// written.  Every shape holds cell (0, 0), so a valid slot has 0 <= x < W and
+// x fits its six bits.
+__device__ __forceinline__ uint32_t placed_piece(int id, int rot, int x, int lock_mod) {
+    return (uint32_t)id | (uint32_t)rot << 3 | (uint32_t)x << 5 | (uint32_t)(lock_mod - 1) << 17;  // anchor row 0
+}
+
+// One lane per env: the piece word, the slot and the slot's four box columns
+// (floor bits, all-ones walls outside [0, W), as stage_env_columns gives them)
+// are the lane's only loads; the piece word leaves with a plain vector store.
+__global__ __launch_bounds__(256) void k_place(KParams p, const int32_t *__restrict__ slots,
+                                               uint8_t *__restrict__ placed) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.n) return;
+    const int W = p.W, per = W + 6;
+    const uint32_t pid = p.piece[e] & 7u;
+    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
+    const int32_t s = slots[e];
+    bool ok = false;
+    if (s >= 0 && s < 4 * per) {
+        const int r = (s >= per) + (s >= 2 * per) + (s >= 3 * per), x = s - r * per - 3;
+        const uint32_t m = c_tab_m[id * 4 + r], g = c_tab_g[id * 4 + r];
+        const int x0 = box_x0(g, x);  // in [-6, W + 2]
+        const uint32_t floorb = ~((1u << p.H) - 1u);
+        uint32_t v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = x0 + j;
+            v[j] = c >= 0 && c < W ? p.board[c * p.stride + e] | floorb : ~0u;
+        }
+        ok = !collides_v(m, 0, v);
+        if (ok) p.piece[e] = placed_piece(id, r, x, p.lock_mod);
+    }
+    if (placed) placed[e] = ok ? 1 : 0;
+}
+
 // ---------------------------------------------------------------- linear feature player
 // st_policy_linear: env e scores every slot of its current piece with weight
 // row e % n_w and keeps the best one -- k_afterstates's evaluation (eval_slot)
@@ -4137,7 +4181,10 @@ struct PassTag {
 #define ST_POLICY_WAVES 4  // envs (waves) per workgroup: the block-shape A/B, DESIGN "Linear feature player"
 #endif
 
-template <int WAVES>
+// COMMIT (st_play_linear_placements): the lane that writes the env's outputs
+// also stores the chosen slot's piece word (placed_piece: k_place's commit,
+// without its launch); it stores nothing if no slot is valid.
+template <int WAVES, bool COMMIT = false>
 __global__ __launch_bounds__(WAVES *kWave) void k_policy_linear(KParams p, const float *__restrict__ wts, int64_t n_w,
                                                                 int32_t *__restrict__ slots,
                                                                 uint8_t *__restrict__ actions,
@@ -4214,6 +4261,12 @@ __global__ __launch_bounds__(WAVES *kWave) void k_policy_linear(KParams p, const
 #pragma unroll
             for (int r = 0; r < ST_AFTER_NFEAT; ++r) best[(size_t)r * p.n + e] = none ? 0 : bf[r];
         }
+        if constexpr (COMMIT) {
+            if (!none) {
+                const int trot = (win >= per) + (win >= 2 * per) + (win >= 3 * per), tx = win - trot * per - 3;
+                p.piece[e] = placed_piece(id, trot, tx, p.lock_mod);
+            }
+        }
     }
 }
 #endif  // ST_AFTERSTATES_TU
@@ -4244,6 +4297,18 @@ hipError_t launch_afterstates(const KParams &p, int32_t *feat, uint32_t *boards,
 
 hipError_t launch_placement_actions(const KParams &p, const int32_t *slots, uint8_t *out, hipStream_t s) {
     hipLaunchKernelGGL(k_placement_actions, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p, slots, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_place(const KParams &p, const int32_t *slots, uint8_t *placed, hipStream_t s) {
+    hipLaunchKernelGGL(k_place, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p, slots, placed);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_linear_commit(const KParams &p, const float *weights, int64_t n_w, hipStream_t s) {
+    constexpr int WV = ST_POLICY_WAVES;
+    hipLaunchKernelGGL((k_policy_linear<WV, true>), dim3((unsigned)((p.n + WV - 1) / WV)), dim3(WV * kWave), 0, s, p,
+                       weights, n_w, (int32_t *)nullptr, (uint8_t *)nullptr, (float *)nullptr, (int32_t *)nullptr);
     return hipGetLastError();
 }
 

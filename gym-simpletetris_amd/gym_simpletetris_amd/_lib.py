@@ -109,6 +109,9 @@ SIG = {
     "st_placement_actions": ([_vp, _vp, _vp, _vp], ctypes.c_int),
     "st_policy_linear": ([_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_play_linear": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_place": ([_vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_step_placements": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_play_linear_placements": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_debug_stamps": ([_vp, _vp, _i64], ctypes.c_int),
     "st_last_error": ([], ctypes.c_char_p),
     "st_abi_version": ([], ctypes.c_int),
@@ -143,7 +146,7 @@ def load(path: str = LIB_PATH):
             if ab_override:
                 continue
             # an addition that did not change the ABI number (st_step_export, st_afterstates,
-            # st_policy_linear):
+            # st_policy_linear, st_place):
             # the library on disk was built before it
             raise ImportError(f"{path}: no symbol {name} (a stale build of ABI {abi}: rebuild it with "
                               "`make -C gym-simpletetris_amd/csrc`)")

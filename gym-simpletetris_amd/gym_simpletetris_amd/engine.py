@@ -311,6 +311,7 @@ class TetrisBatch:
         self.done = torch.zeros(n, dtype=torch.bool, device=device)
         self._act = torch.zeros(n, dtype=torch.uint8, device=device)
         self._place_act: Optional[torch.Tensor] = None  # placement_actions' reused output (made on first use)
+        self.placed: Optional[torch.Tensor] = None  # place() / step_placements(): uint8 [n] commit flags (made on first use)
         self._seeded = False
         if seeds is not None:
             self.seed(seeds)
@@ -769,14 +770,10 @@ class TetrisBatch:
         C.check(self._L.st_afterstates(self._ctx, _ptr(feat), _ptr(brd), self._stream()))
         return Afterstates(feat, brd)
 
-    def placement_actions(self, slots, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The action (uint8 [n], as step() takes it) that moves each env's
-        live piece toward its placement slot (st_placement_actions):
-        rotate_left (4) until the rotation is the slot's, then right (1) /
-        left (0) toward its column, then hard drop (2) -- the greedy
-        policy's rule; a slot outside [0, n_slots) (e.g. -1: no valid
-        placement) hard-drops.  slots: [n] integers, a device tensor (int32
-        as it is) or a host sequence."""
+    def _slots(self, slots) -> torch.Tensor:
+        """Placement slots as a contiguous int32 device tensor [n]: a device
+        int32 tensor as it is, another integer tensor or a host sequence
+        converted."""
         if isinstance(slots, torch.Tensor):
             if slots.is_floating_point() or slots.is_complex() or slots.dtype == torch.bool:
                 raise TypeError(f"slots must be integers, got {slots.dtype}")
@@ -785,6 +782,17 @@ class TetrisBatch:
             s = torch.as_tensor(np.asarray(slots).astype(np.int32), device=self.device)
         if tuple(s.shape) != (self.n,):
             raise ValueError(f"slots must have shape ({self.n},), got {tuple(s.shape)}")
+        return s
+
+    def placement_actions(self, slots, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The action (uint8 [n], as step() takes it) that moves each env's
+        live piece toward its placement slot (st_placement_actions):
+        rotate_left (4) until the rotation is the slot's, then right (1) /
+        left (0) toward its column, then hard drop (2) -- the greedy
+        policy's rule; a slot outside [0, n_slots) (e.g. -1: no valid
+        placement) hard-drops.  slots: [n] integers, a device tensor (int32
+        as it is) or a host sequence."""
+        s = self._slots(slots)
         if out is None:
             if self._place_act is None:
                 self._place_act = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
@@ -793,6 +801,51 @@ class TetrisBatch:
             _check_tensor(out, "out", (self.n,), (torch.uint8,), self.device)
         C.check(self._L.st_placement_actions(self._ctx, _ptr(s), _ptr(out), self._stream()))
         return out
+
+    # ------------------------------------------------------------ placement step
+    def _placed_out(self, out) -> torch.Tensor:
+        if out is None:
+            if self.placed is None:
+                self.placed = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+            return self.placed
+        _check_tensor(out, "out placed", (self.n,), (torch.uint8,), self.device)
+        return out
+
+    def place(self, slots, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Commit a placement slot per env (st_place), without stepping.  A
+        valid slot -- in [0, n_slots) and, as in afterstates(), not occupied
+        at (x, 0) on the env's board for its current piece -- teleports the
+        env's piece there: rotation rot, anchor (x, 0) and a lock counter of
+        max(lock_delay, 0), so that the next hard drop locks it whatever
+        lock_delay is.  Any other slot (occupied, out of range, -1) leaves
+        the piece exactly as it is.  Board, counters and MT are not touched.
+        slots: [n] integers as placement_actions takes them.  Returns `placed`
+        uint8 [n] (1: committed) -- a reused buffer, or the caller's `out`."""
+        s = self._slots(slots)
+        placed = self._placed_out(out)
+        C.check(self._L.st_place(self._ctx, _ptr(s), _ptr(placed), self._stream()))
+        return placed
+
+    def step_placements(self, slots, obs: str = "packed", out=None):
+        """One placement step on every env (st_step_placements): place(slots),
+        then TetrisEngine.step(hard_drop) -- one decision is one piece.  Where
+        the slot is valid the piece locks in this step, the reward is the
+        slot's afterstates().reward and the board becomes its afterstate
+        (before a death's erase or same-step reset), and the next piece is
+        drawn; where it is not, the live piece hard-drops as it is.  Returns
+        what step() returns -- (obs, reward, done), obs 'packed' or 'none',
+        `out` as for step() -- and leaves the uint8 [n] commit flags in
+        .placed.  Never raises for actions (they are the library's own)."""
+        if obs not in ("packed", "none"):
+            raise ValueError("obs must be 'packed' or 'none'")
+        s = self._slots(slots)
+        o_t, r_t, d_t = (self.obs, self.reward, self.done) if out is None \
+            else _check_out(out, self.width, self.n, self.device)
+        placed = self._placed_out(None)
+        o_ret = o_t if obs == "packed" else None
+        C.check(self._L.st_step_placements(self._ctx, _ptr(s), _ptr(placed), _ptr(o_ret), _ptr(r_t), _ptr(d_t),
+                                           self._stream()))
+        return o_ret, r_t, d_t
 
     # ------------------------------------------------------------ linear feature players
     def _weights(self, weights) -> torch.Tensor:
@@ -846,7 +899,7 @@ class TetrisBatch:
         return LinearChoice(sl, ac, sc, ft)
 
     def play_linear(self, weights, k: int, returns: Optional[torch.Tensor] = None,
-                    episodes: Optional[torch.Tensor] = None, obs: str = "none"):
+                    episodes: Optional[torch.Tensor] = None, obs: str = "none", placements: bool = False):
         """k steps of policy_linear(weights) -> step, enqueued by ONE library
         call (st_play_linear: no Python, no host read-back between the steps),
         identical to k rounds of policy_linear + step by hand.  Adds every
@@ -860,7 +913,12 @@ class TetrisBatch:
         are in .reward, .done and (obs='packed') .obs.  Not gated, never
         raises for actions (the policy's are 0..6); k = 0 does nothing.  The
         library keeps the actions and the rows it sums in one buffer per
-        batch: keep a batch's play_linear calls on one stream."""
+        batch: keep a batch's play_linear calls on one stream.
+        placements=True plays at placement level (st_play_linear_placements):
+        k rounds of policy_linear -> step_placements(its slots), the policy's
+        launch committing its own choice -- every iteration locks a piece
+        (where a slot is valid) and pays exactly the afterstate reward the
+        policy maximised; two launches per piece."""
         if obs not in ("packed", "none"):
             raise ValueError("obs must be 'packed' or 'none'")
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
@@ -874,9 +932,9 @@ class TetrisBatch:
             episodes = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         else:
             _check_tensor(episodes, "episodes", (self.n,), (torch.int32,), self.device)
-        C.check(self._L.st_play_linear(self._ctx, _ptr(w), w.shape[0], int(k), _ptr(returns), _ptr(episodes),
-                                       _ptr(self.obs) if obs == "packed" else None, _ptr(self.reward),
-                                       _ptr(self.done), self._stream()))
+        fn = self._L.st_play_linear_placements if placements else self._L.st_play_linear
+        C.check(fn(self._ctx, _ptr(w), w.shape[0], int(k), _ptr(returns), _ptr(episodes),
+                 _ptr(self.obs) if obs == "packed" else None, _ptr(self.reward), _ptr(self.done), self._stream()))
         return returns, episodes
 
 

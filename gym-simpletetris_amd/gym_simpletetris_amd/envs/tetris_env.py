@@ -552,12 +552,25 @@ class TetrisVecEnv:
         feature row) in one launch."""
         return self.engine.policy_linear(weights, out=out)
 
-    def play_linear(self, weights, k, returns=None, episodes=None, obs="none"):
+    def play_linear(self, weights, k, returns=None, episodes=None, obs="none", placements=False):
         """TetrisBatch.play_linear of the engine: k steps of policy_linear ->
         step in one library call, straight on the engine (no info, no
         final_observation: with autoreset a finished env simply plays on);
-        returns the (returns, episodes) accumulators."""
-        return self.engine.play_linear(weights, k, returns=returns, episodes=episodes, obs=obs)
+        returns the (returns, episodes) accumulators.  placements=True: at
+        placement level (policy_linear -> step_placements)."""
+        return self.engine.play_linear(weights, k, returns=returns, episodes=episodes, obs=obs,
+                                       placements=placements)
+
+    def place(self, slots, out=None):
+        """TetrisBatch.place of the engine, on its stream: commit a placement
+        slot per env (the piece is teleported there), without stepping."""
+        return self.engine.place(slots, out=out)
+
+    def step_placements(self, slots, obs="packed", out=None):
+        """TetrisBatch.step_placements of the engine: place(slots), then the
+        hard drop that locks the piece, straight on the engine (no info, no
+        final_observation); returns its (obs, reward, done)."""
+        return self.engine.step_placements(slots, obs=obs, out=out)
 
     def close(self):
         self._pool.clear()

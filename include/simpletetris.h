@@ -36,8 +36,9 @@ extern "C" {
  * st_stream_wait (additions only).  4: st_step_n (addition only).
  * st_step_export: addition only, version unchanged (a build without it is
  * refused by the host package when it binds the symbol); so are
- * st_after_slots / st_afterstates / st_placement_actions and
- * st_policy_linear / st_play_linear.
+ * st_after_slots / st_afterstates / st_placement_actions,
+ * st_policy_linear / st_play_linear and st_place / st_step_placements /
+ * st_play_linear_placements.
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -422,7 +423,8 @@ int st_policy_linear(st_ctx *ctx, const float *d_weights, int64_t n_w,
 
 /* k times (st_policy_linear -> st_step), enqueued by one host call: iteration
  * i writes the policy's actions into a buffer the context owns (allocated on
- * the first call, freed by st_destroy) and runs the ordinary step on them.
+ * the first call, which also waits for the stream once -- see
+ * st_step_placements; freed by st_destroy) and runs the ordinary step on them.
  * d_return   int64 [n_envs] or NULL: += the reward of every one of the k steps.
  * d_episodes int32 [n_envs] or NULL: += the done of every one of the k steps.
  *   Both add to what the caller left in them, so consecutive calls chain
@@ -445,6 +447,66 @@ int st_policy_linear(st_ctx *ctx, const float *d_weights, int64_t n_w,
 int st_play_linear(st_ctx *ctx, const float *d_weights, int64_t n_w, int64_t k,
                    int64_t *d_return, int32_t *d_episodes,
                    uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
+
+/* Placement step: the game the afterstate literature plays -- one decision is
+ * one piece, the action is the placement, the transition is the afterstate
+ * plus the next piece -- defined in the reference's own terms only.
+ *
+ * COMMITTING slot s of env e, s = rot * (W + 6) + (x + 3) as in st_afterstates:
+ *  - VALID slot: s in [0, S) and not is_occupied(rotated^rot(shapes[id]),
+ *    (x, 0), board) (tetris_env.py:29-36) -- the very validity rule of
+ *    st_afterstates, on the env's current board and piece id.  The env's piece
+ *    becomes: shape = rot applications of rotated(cclk=False) to the base shape
+ *    (:22-26); anchor = (x, 0); _lock_delay = max(lock_delay, 0), so that
+ *    _lock_delay_fn (:175) returns 0 on the next drop and the piece locks in
+ *    that step whatever lock_delay is.  As a piece word:
+ *    id | rot << 3 | x << 5 | 0 << 11 | max(lock_delay, 0) << 17.  Every shape
+ *    holds cell (0, 0), so a valid slot has 0 <= x < W and fits the field.
+ *  - INVALID slot (occupied at row 0, outside [0, S), e.g. -1): the piece is
+ *    left exactly as it is, lock counter included.
+ * Nothing else changes: board, counters, MT, preview.
+ *
+ * A PLACEMENT STEP is a commit followed by TetrisEngine.step(2) (hard_drop,
+ * :243-304).  For a valid slot it follows from the reference that the piece
+ * locks in this step (time + 1), the reward is that slot's ST_AFTER_REWARD,
+ * the board after the step is that slot's st_afterstates board (before the
+ * death erase, :303, or the same-step reset), the next piece is drawn, and
+ * under ST_AUTORESET_SAME_STEP a death resets inside the step as usual.  For
+ * an invalid slot the step is an ordinary hard drop of the live piece (as
+ * st_placement_actions gives 2 for a slot outside [0, S) and st_policy_linear
+ * for slot -1); with lock_delay > 0 it need not lock.
+ *
+ * st_place: the commit alone, one launch.  d_slots int32 [n_envs]; d_placed
+ * uint8 [n_envs] or NULL: 1 where the slot was valid and committed, else 0.
+ * It reads the board and writes the piece row only; a host-written piece id 7
+ * is read as 6, as in st_afterstates.  ST_EINVAL for a NULL ctx or d_slots,
+ * ST_ESTATE before st_seed + st_reset, both before any GPU call; not gated,
+ * consumes no gate, needs no st_mt_sync. */
+int st_place(st_ctx *ctx, const int32_t *d_slots, uint8_t *d_placed, st_stream stream);
+/* st_place, then the ordinary step (st_step's kernel, unchanged) on a buffer
+ * the context owns that holds action 2 for every env (part of st_play_linear's
+ * allocation: made and filled on first use, freed by st_destroy): two
+ * launches.  The context's FIRST call of st_play_linear, st_step_placements
+ * or st_play_linear_placements allocates that buffer, fills it on `stream`
+ * and waits for the stream (hipStreamSynchronize): it is not asynchronous
+ * and must not be made while the stream is being captured; later calls only
+ * enqueue.  d_placed as for st_place; d_obs / d_reward / d_done as st_step
+ * writes them, any of them NULL.  The step is not gated and an armed
+ * st_gate_actions stays armed; the st_set_action_flag word is honoured.
+ * Errors as for st_place. */
+int st_step_placements(st_ctx *ctx, const int32_t *d_slots, uint8_t *d_placed,
+                       uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
+/* st_play_linear at placement level: k times (st_policy_linear's choice,
+ * committed by the same launch -> the step on the constant hard drop), two
+ * launches per piece, identical to k rounds of st_policy_linear +
+ * st_step_placements(its d_slots) by hand; where no slot is valid (slot -1)
+ * nothing is committed and the live piece hard-drops.  d_return, d_episodes,
+ * the last step's d_obs / d_reward / d_done, the one-buffer-per-context
+ * ordering rule, both autoreset modes, k <= 0 and the errors are
+ * st_play_linear's, word for word. */
+int st_play_linear_placements(st_ctx *ctx, const float *d_weights, int64_t n_w, int64_t k,
+                              int64_t *d_return, int32_t *d_episodes,
+                              uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
 
 /* Synthetic action source used by the benchmark and the parity tests:
  * d_out[e] = splitmix64(seed ^ ((t << 32) ^ (global_offset + e))) % 7. */
