@@ -593,6 +593,26 @@ int st_placement_actions(st_ctx *c, const int32_t *d_slots, uint8_t *d_actions, 
     return ST_OK;
 }
 
+int st_reachable(st_ctx *c, int32_t *d_steps, uint8_t *d_first, st_stream stream) {
+    if (!c || !d_steps) return fail(ST_EINVAL, "st_reachable: null argument");
+    if (c->cfg.lock_delay > ST_REACH_MAX_LOCK)
+        return fail(ST_EINVAL, "st_reachable: lock_delay %d > %d", c->cfg.lock_delay, ST_REACH_MAX_LOCK);
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_reachable before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    ST_HIP(st::launch_reachable(params(c), d_steps, d_first, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_route_actions(st_ctx *c, const int32_t *d_slots, uint8_t *d_actions, int32_t *d_steps, st_stream stream) {
+    if (!c || !d_slots || !d_actions) return fail(ST_EINVAL, "st_route_actions: null argument");
+    if (c->cfg.lock_delay > ST_REACH_MAX_LOCK)
+        return fail(ST_EINVAL, "st_route_actions: lock_delay %d > %d", c->cfg.lock_delay, ST_REACH_MAX_LOCK);
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_route_actions before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    ST_HIP(st::launch_route_actions(params(c), d_slots, d_actions, d_steps, (hipStream_t)stream));
+    return ST_OK;
+}
+
 int st_policy_linear(st_ctx *c, const float *d_weights, int64_t n_w, int32_t *d_slots, uint8_t *d_actions,
                      float *d_scores, int32_t *d_best, st_stream stream) {
     if (!c || !d_weights) return fail(ST_EINVAL, "st_policy_linear: null argument");

@@ -105,6 +105,11 @@ hipError_t launch_policy_linear_commit(const KParams &p, const float *weights, i
 // int64 [n] / acc_episodes int32 [n] (either null) and copies the last row to out_reward / out_done (either null)
 hipError_t launch_play_sum(const KParams &p, const int32_t *reward, const uint8_t *done, int rows, int64_t *acc_return,
                            int32_t *acc_episodes, int32_t *out_reward, uint8_t *out_done, hipStream_t s);
+// st_reachable: steps int32 [n][S]; first uint8 [n][S] or null (then the untagged search)
+hipError_t launch_reachable(const KParams &p, int32_t *steps, uint8_t *first, hipStream_t s);
+// st_route_actions: slots int32 [n], actions uint8 [n]; steps int32 [n] or null
+hipError_t launch_route_actions(const KParams &p, const int32_t *slots, uint8_t *actions, int32_t *steps,
+                                hipStream_t s);
 hipError_t launch_grayscale(const KParams &p, const uint32_t *obs, int size, int channels,
                             int as_u8, void *out, hipStream_t s);
 hipError_t launch_unwire(int W, int H, int64_t n_global, int shards, int64_t n_cap, const uint32_t *wire,

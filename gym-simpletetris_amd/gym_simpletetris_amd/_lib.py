@@ -43,6 +43,7 @@ EXPORT_MT, EXPORT_OBS_F32 = 1, 2  # st_export_env parts
 AFTER = dict(valid=0, y=1, lines=2, holes=3, height=4, rows=5, above=6, dead=7, reward=8, agg_height=9,
              bumpiness=10)
 AFTER_NFEAT = 11
+REACH_MAX_LOCK = 3  # ST_REACH_MAX_LOCK: the largest lock_delay st_reachable / st_route_actions take
 
 
 class StError(RuntimeError):
@@ -107,6 +108,8 @@ SIG = {
     "st_after_slots": ([_i32], ctypes.c_int),
     "st_afterstates": ([_vp, _vp, _vp, _vp], ctypes.c_int),
     "st_placement_actions": ([_vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_reachable": ([_vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_route_actions": ([_vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_policy_linear": ([_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_play_linear": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_place": ([_vp, _vp, _vp, _vp], ctypes.c_int),
@@ -146,7 +149,7 @@ def load(path: str = LIB_PATH):
             if ab_override:
                 continue
             # an addition that did not change the ABI number (st_step_export, st_afterstates,
-            # st_policy_linear, st_place):
+            # st_policy_linear, st_place, st_reachable):
             # the library on disk was built before it
             raise ImportError(f"{path}: no symbol {name} (a stale build of ABI {abi}: rebuild it with "
                               "`make -C gym-simpletetris_amd/csrc`)")

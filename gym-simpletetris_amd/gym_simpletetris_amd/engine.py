@@ -176,6 +176,21 @@ class Afterstates:
         return self.feat[:, row]
 
 
+class Reachable:
+    """TetrisBatch.reachable()'s result: `steps` int32 [n, S] (the length of the
+    shortest action sequence that locks the live piece in the slot, 0 where
+    none does) and `first` uint8 [n, S] (the lowest-numbered action that begins
+    one, 2 where none does; None with first=False), slot innermost; `mask`
+    is steps > 0."""
+
+    def __init__(self, steps: torch.Tensor, first: Optional[torch.Tensor]):
+        self.steps, self.first = steps, first
+
+    @property
+    def mask(self) -> torch.Tensor:
+        return self.steps > 0
+
+
 # st_policy_greedy's score as linear feature weights: 80 * lines - 12 * holes
 # - 3 * height - 2000 * above (rows by their names in _lib.AFTER)
 GREEDY_WEIGHTS = MappingProxyType(dict(lines=80.0, holes=-12.0, height=-3.0, above=-2000.0))
@@ -311,6 +326,7 @@ class TetrisBatch:
         self.done = torch.zeros(n, dtype=torch.bool, device=device)
         self._act = torch.zeros(n, dtype=torch.uint8, device=device)
         self._place_act: Optional[torch.Tensor] = None  # placement_actions' reused output (made on first use)
+        self._route_act: Optional[torch.Tensor] = None  # route_actions' reused output (made on first use)
         self.placed: Optional[torch.Tensor] = None  # place() / step_placements(): uint8 [n] commit flags (made on first use)
         self._seeded = False
         if seeds is not None:
@@ -800,6 +816,56 @@ class TetrisBatch:
         else:
             _check_tensor(out, "out", (self.n,), (torch.uint8,), self.device)
         C.check(self._L.st_placement_actions(self._ctx, _ptr(s), _ptr(out), self._stream()))
+        return out
+
+    # ------------------------------------------------------------ reachability
+    def reachable(self, first: bool = True, out=None) -> Reachable:
+        """Which placement slots each env's live piece can really be locked in
+        under the reference's step (st_reachable): a slot of afterstates() is
+        reachable iff it is valid and some action sequence from the piece's
+        present (rot, x, y, lock counter) -- each step the action, then
+        gravity, then the lock rule (tetris_env.py:243-262) -- locks the piece
+        at the slot's landing.  Returns a Reachable: steps int32 [n, S], the
+        shortest such sequence's length (0: unreachable), with `first` the
+        lowest-numbered action uint8 [n, S] that begins one (2: unreachable),
+        and .mask = steps > 0.  first=False searches the distances alone,
+        which is cheaper.  Reads the state, changes none of it; lock_delay
+        above REACH_MAX_LOCK is refused.  `out`: a (steps, first) pair of
+        device tensors to write (first None with first=False)."""
+        n, S = self.n, self.n_slots
+        if out is None:
+            steps = torch.empty((n, S), dtype=torch.int32, device=self.device)
+            fst = torch.empty((n, S), dtype=torch.uint8, device=self.device) if first else None
+        else:
+            steps, fst = out
+            _check_tensor(steps, "out steps", (n, S), (torch.int32,), self.device)
+            if first:
+                _check_tensor(fst, "out first", (n, S), (torch.uint8,), self.device)
+            elif fst is not None:
+                raise ValueError("out first given with first=False")
+        C.check(self._L.st_reachable(self._ctx, _ptr(steps), _ptr(fst), self._stream()))
+        return Reachable(steps, fst)
+
+    def route_actions(self, slots, out: Optional[torch.Tensor] = None,
+                      steps: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The action (uint8 [n], as step() takes it) that begins a shortest
+        way of each env's live piece into its placement slot
+        (st_route_actions): reachable()'s `first` of that slot; 2 (hard drop)
+        for a slot outside [0, n_slots), invalid or unreachable.  Stepping
+        with it and asking again locks the piece there after exactly
+        reachable().steps steps.  slots: as placement_actions takes them;
+        `steps`: an int32 [n] device tensor that receives the slot's steps
+        (0 likewise)."""
+        s = self._slots(slots)
+        if out is None:
+            if self._route_act is None:
+                self._route_act = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+            out = self._route_act
+        else:
+            _check_tensor(out, "out", (self.n,), (torch.uint8,), self.device)
+        if steps is not None:
+            _check_tensor(steps, "steps", (self.n,), (torch.int32,), self.device)
+        C.check(self._L.st_route_actions(self._ctx, _ptr(s), _ptr(out), _ptr(steps), self._stream()))
         return out
 
     # ------------------------------------------------------------ placement step

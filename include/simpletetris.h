@@ -37,8 +37,8 @@ extern "C" {
  * st_step_export: addition only, version unchanged (a build without it is
  * refused by the host package when it binds the symbol); so are
  * st_after_slots / st_afterstates / st_placement_actions,
- * st_policy_linear / st_play_linear and st_place / st_step_placements /
- * st_play_linear_placements.
+ * st_policy_linear / st_play_linear, st_place / st_step_placements /
+ * st_play_linear_placements and st_reachable / st_route_actions.
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -382,6 +382,56 @@ int st_afterstates(st_ctx *ctx, int32_t *d_feat, uint32_t *d_boards, st_stream s
  * st_placement_actions -> st_step, repeated, plays the chosen placement out.
  * NULL checks and ST_ESTATE as for st_afterstates. */
 int st_placement_actions(st_ctx *ctx, const int32_t *d_slots, uint8_t *d_actions, st_stream stream);
+
+/* Reachability: which placement slots the live piece can really be locked in
+ * under the reference's own step, in how many steps, and how to start.
+ *
+ * Let L = max(lock_delay, 0).  The live piece's state is (rot, x, y, l):
+ * rotation, anchor and the lock counter _lock_delay, as in the piece word.
+ * One TetrisEngine.step(a) (tetris_env.py:243-304) acts on it, with the board
+ * fixed, as follows:
+ *  1. the action (:245): left / right / hard_drop / soft_drop / rotate_left /
+ *     rotate_right / idle (:39-73), each keeping the old position where
+ *     is_occupied (:29-36) refuses the new one;
+ *  2. gravity, soft_drop (:247); if it moved the piece and step_reset is on,
+ *     l = 0 (:248);
+ *  3. if _has_dropped() (:259): l = (l + 1) % (L + 1); if that is 0 the piece
+ *     LOCKS at its (rot, x, y), else the step ends in state (rot, x, y, l).
+ * The start state need not be collision-free (a spawn onto the stack, a
+ * host-written piece): the rules only ever test the destination.
+ *
+ * Slot s = rot * (W + 6) + (x + 3) of st_afterstates is REACHABLE iff it is
+ * valid and some action sequence from the env's present piece state locks the
+ * piece at (rot, x, ST_AFTER_Y[s]).
+ *   steps[s]: the length of the shortest such sequence, the locking step
+ *             counted (so >= 1); 0 where the slot is not reachable.
+ *   first[s]: the lowest-numbered action that begins a shortest sequence; 2
+ *             where the slot is not reachable (as st_placement_actions gives
+ *             for a slot it cannot serve).
+ * It follows that after first[s] the target is steps[s] - 1 away, and that
+ * locking there leaves exactly that slot's afterstate board and, in that step,
+ * its ST_AFTER_REWARD.  Lock positions that are no slot's landing (a tuck under
+ * an overhang) are outside the slot set and are not reported.
+ *
+ * Both calls follow st_afterstates: they read the state enqueued before them
+ * on `stream` and change none of it (board, piece, counters, MT, preview), need
+ * no st_mt_sync, are not gated and consume no gate; a host-written piece id 7
+ * is read as 6.  ST_EINVAL for a NULL ctx or a NULL required pointer and for
+ * max(lock_delay, 0) > ST_REACH_MAX_LOCK, ST_ESTATE before st_seed + st_reset,
+ * all before any GPU call.  A host-written lock counter above L gives an
+ * unspecified result, except that every steps stays >= 0, every first in 0..6
+ * and nothing faults. */
+#define ST_REACH_MAX_LOCK 3   /* the largest lock_delay the search takes */
+/* d_steps int32 [n_envs][S], required; d_first uint8 [n_envs][S] or NULL (then
+ * only the distances are searched, which is cheaper).  Slot innermost, like
+ * d_feat. */
+int st_reachable(st_ctx *ctx, int32_t *d_steps, uint8_t *d_first, st_stream stream);
+/* d_actions[e] (uint8 [n_envs], required) = first[d_slots[e]] of env e: 2 for a
+ * slot outside [0, S), invalid, or unreachable.  d_steps int32 [n_envs] or
+ * NULL: steps[d_slots[e]] (0 likewise).  route_actions -> st_step, repeated,
+ * locks the piece in a reachable slot after exactly steps[s] steps, d_steps
+ * falling by one a step. */
+int st_route_actions(st_ctx *ctx, const int32_t *d_slots, uint8_t *d_actions, int32_t *d_steps, st_stream stream);
 
 /* Linear feature player (Dellacherie / BCTS players, CEM or ES over feature
  * weights): env e scores every placement slot of its current piece with
