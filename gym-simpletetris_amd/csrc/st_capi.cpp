@@ -629,10 +629,12 @@ int st_policy_linear(st_ctx *c, const float *d_weights, int64_t n_w, int32_t *d_
 // st_play_linear (commit false: the policy's primitive action, then the step
 // on it) and st_play_linear_placements (commit true: the policy commits its
 // slot, then the step on the constant hard drop)
+// set: the rows the policy scores (st_play_linear_set; the base set runs the two older kernels)
 static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weights, int64_t n_w, int64_t k,
                      int64_t *d_return, int32_t *d_episodes, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
-                     st_stream stream) {
+                     st_stream stream, int32_t set = ST_FEATS_BASE) {
     if (!c || !d_weights) return fail(ST_EINVAL, "%s: null argument", fn);
+    if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS) return fail(ST_EINVAL, "%s: unknown feature set %d", fn, set);
     if (n_w < 1) return fail(ST_EINVAL, "%s: n_w %lld < 1", fn, (long long)n_w);
     if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "%s before st_seed + st_reset", fn);
     if (k <= 0) return ST_OK;
@@ -651,7 +653,10 @@ static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weig
     int row = 0;
     for (int64_t i = 0; i < k; ++i) {
         const bool last = i == k - 1;
-        if (commit) ST_HIP(st::launch_policy_linear_commit(params(c), d_weights, n_w, s));
+        if (set != ST_FEATS_BASE)
+            ST_HIP(st::launch_policy_linear_set(params(c), set, commit, d_weights, n_w, nullptr, nullptr,
+                                                commit ? nullptr : q.act, nullptr, nullptr, s));
+        else if (commit) ST_HIP(st::launch_policy_linear_commit(params(c), d_weights, n_w, s));
         else ST_HIP(st::launch_policy_linear(params(c), d_weights, n_w, nullptr, q.act, nullptr, nullptr, s));
         int32_t *rew = acc || !d_reward ? q.ring_rew + (int64_t)row * n : d_reward;
         uint8_t *done = acc || !d_done ? q.ring_done + (int64_t)row * n : d_done;
@@ -679,6 +684,51 @@ int st_play_linear_placements(st_ctx *c, const float *d_weights, int64_t n_w, in
                               st_stream stream) {
     return play_impl(c, "st_play_linear_placements", true, d_weights, n_w, k, d_return, d_episodes, d_obs, d_reward,
                      d_done, stream);
+}
+
+int st_feature_rows(int32_t set) {
+    if (set == ST_FEATS_BASE) return ST_AFTER_NFEAT;
+    if (set == ST_FEATS_BCTS) return ST_AFTER_NFEAT + ST_AFTER_NEXT;
+    return fail(ST_EINVAL, "st_feature_rows: unknown feature set %d", set);
+}
+
+int st_afterstates_set(st_ctx *c, int32_t set, int32_t *d_feat, uint32_t *d_boards, st_stream stream) {
+    if (!c || !d_feat) return fail(ST_EINVAL, "st_afterstates_set: null argument");
+    if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS)
+        return fail(ST_EINVAL, "st_afterstates_set: unknown feature set %d", set);
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_afterstates_set before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_afterstates_set: hipSetDevice(%d) failed", c->device);
+    if (set == ST_FEATS_BASE) ST_HIP(st::launch_afterstates(params(c), d_feat, d_boards, (hipStream_t)stream));
+    else ST_HIP(st::launch_afterstates_set(params(c), set, d_feat, d_boards, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_policy_linear_set(st_ctx *c, int32_t set, const float *d_weights, int64_t n_w, const int32_t *d_allowed,
+                         int32_t *d_slots, uint8_t *d_actions, float *d_scores, int32_t *d_best, st_stream stream) {
+    if (!c || !d_weights) return fail(ST_EINVAL, "st_policy_linear_set: null argument");
+    if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS)
+        return fail(ST_EINVAL, "st_policy_linear_set: unknown feature set %d", set);
+    if (n_w < 1) return fail(ST_EINVAL, "st_policy_linear_set: n_w %lld < 1", (long long)n_w);
+    if (!d_slots && !d_actions && !d_scores && !d_best)
+        return fail(ST_EINVAL, "st_policy_linear_set: every output is null");
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_policy_linear_set before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_policy_linear_set: hipSetDevice(%d) failed", c->device);
+    if (set == ST_FEATS_BASE && !d_allowed)  // st_policy_linear's own kernel
+        ST_HIP(st::launch_policy_linear(params(c), d_weights, n_w, d_slots, d_actions, d_scores, d_best,
+                                        (hipStream_t)stream));
+    else
+        ST_HIP(st::launch_policy_linear_set(params(c), set, false, d_weights, n_w, d_allowed, d_slots, d_actions,
+                                            d_scores, d_best, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_play_linear_set(st_ctx *c, int32_t set, const float *d_weights, int64_t n_w, int64_t k, int32_t placements,
+                       int64_t *d_return, int32_t *d_episodes, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
+                       st_stream stream) {
+    return play_impl(c, "st_play_linear_set", placements != 0, d_weights, n_w, k, d_return, d_episodes, d_obs,
+                     d_reward, d_done, stream, set);
 }
 
 int st_place(st_ctx *c, const int32_t *d_slots, uint8_t *d_placed, st_stream stream) {

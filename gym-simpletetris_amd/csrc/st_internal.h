@@ -101,6 +101,14 @@ hipError_t launch_policy_linear(const KParams &p, const float *weights, int64_t 
 hipError_t launch_place(const KParams &p, const int32_t *slots, uint8_t *placed, hipStream_t s);
 // st_play_linear_placements: st_policy_linear's choice, committed like launch_place; no other output
 hipError_t launch_policy_linear_commit(const KParams &p, const float *weights, int64_t n_w, hipStream_t s);
+// st_afterstates_set, set = ST_FEATS_BCTS (the base set is launch_afterstates): feat int32 [n][18][S]
+hipError_t launch_afterstates_set(const KParams &p, int set, int32_t *feat, uint32_t *boards, hipStream_t s);
+// st_policy_linear_set / st_play_linear_set: launch_policy_linear (commit: and launch_policy_linear_commit) over the
+// rows of `set` -- weights float [n_w][rows], best int32 [rows][n] -- and with allowed int32 [n][S] or null; the base
+// set takes no commit here (launch_policy_linear_commit is that)
+hipError_t launch_policy_linear_set(const KParams &p, int set, bool commit, const float *weights, int64_t n_w,
+                                    const int32_t *allowed, int32_t *slots, uint8_t *actions, float *scores,
+                                    int32_t *best, hipStream_t s);
 // st_play_linear: adds rows 0 .. rows - 1 of reward int32 [rows][n] / done uint8 [rows][n] to acc_return
 // int64 [n] / acc_episodes int32 [n] (either null) and copies the last row to out_reward / out_done (either null)
 hipError_t launch_play_sum(const KParams &p, const int32_t *reward, const uint8_t *done, int rows, int64_t *acc_return,

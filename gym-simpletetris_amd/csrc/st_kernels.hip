@@ -17,12 +17,14 @@
 // each side are all-ones walls, so a collision test is four AND-tests with no
 // bounds checks and hard_drop is a count-trailing-zeros per piece column.
 //
-// Four translation units are built from this file: the library's kernels (as
+// Five translation units are built from this file: the library's kernels (as
 // it is); with ST_STEP_EXPORT_TU defined (st_step_export.hip), k_step_export
 // and its launcher alone; with ST_AFTERSTATES_TU defined (st_afterstates.hip),
 // k_afterstates, k_placement_actions, k_place, k_policy_linear, k_play_sum and
 // their launchers alone; with ST_REACHABLE_TU defined (st_reachable.hip),
-// k_reachable's instantiations and their launchers alone.  step_logic /
+// k_reachable's instantiations and their launchers alone; with
+// ST_FEATURES_TU defined (st_features.hip), the extended-feature-set kernels
+// (k_afterstates_set, k_policy_linear_set) and their launchers alone.  step_logic /
 // step_draw are shared source, but a second kernel instantiating them in ONE
 // module changes the code the compiler emits for k_step itself (it did: four
 // instructions around the lock ballot's LDS read); in a module of its own a
@@ -30,8 +32,11 @@
 // k_rollout2.
 #include "st_internal.h"
 
-#if defined(ST_STEP_EXPORT_TU) || defined(ST_AFTERSTATES_TU) || defined(ST_REACHABLE_TU)
+#if defined(ST_STEP_EXPORT_TU) || defined(ST_AFTERSTATES_TU) || defined(ST_REACHABLE_TU) || defined(ST_FEATURES_TU)
 #define ST_SIDE_TU 1  // not the library's own translation unit
+#endif
+#if defined(ST_AFTERSTATES_TU) || defined(ST_FEATURES_TU)
+#define ST_EVAL_TU 1  // the translation units that evaluate slots (eval_slot)
 #endif
 
 
@@ -3894,7 +3899,7 @@ __global__ __launch_bounds__(kWave) void k_policy_greedy(KParams p, uint64_t see
 }
 #endif  // !ST_SIDE_TU
 
-#ifdef ST_AFTERSTATES_TU
+#ifdef ST_EVAL_TU
 // ---------------------------------------------------------------- afterstates
 // st_afterstates: what k_policy_greedy evaluates and throws away, as an
 // output.  For env e's board and current piece id, every placement slot
@@ -3984,9 +3989,142 @@ __device__ __forceinline__ bool eval_slot(const uint32_t *C, int W, int H, uint3
     f[ST_AFTER_BUMPINESS] = bump;
     return valid;
 }
-#endif  // ST_AFTERSTATES_TU
 
-#if defined(ST_AFTERSTATES_TU) || defined(ST_REACHABLE_TU)
+// eval_slot_set<SET>: eval_slot with the rows of a feature set, for the
+// kernels of st_features.hip.  It restates eval_slot (which stays word for word
+// what k_afterstates and k_policy_linear were compiled from: a set parameter
+// on eval_slot itself, every extension statement under if constexpr, moved
+// three instructions of theirs) and must follow it change for change; the
+// tests hold the base rows of both against the same oracle.
+// SET = ST_FEATS_BCTS adds the rows of st_after_ext (simpletetris.h, "Feature
+// sets") behind st_after_feat's, from what the walks hold anyway: LANDING2 and
+// ERODED from the piece's box bytes / box bits and the full-row mask, the
+// other five from the column words of the second walk -- a column's word,
+// its left neighbour's and the one before that (a well of column c - 1 is
+// known once column c is), walls as all-ones words of H bits.
+constexpr int feat_rows(int set) { return set == ST_FEATS_BCTS ? ST_AFTER_NFEAT + ST_AFTER_NEXT : ST_AFTER_NFEAT; }
+
+// sum of d (d + 1) / 2 over the runs of set bits of m, d a run's length
+__device__ __forceinline__ int32_t well_sum(uint32_t m) {
+    int32_t sum = 0;
+    while (m) {
+        sum += __builtin_popcount(m);
+        m &= m << 1;
+    }
+    return sum;
+}
+
+// the extension rows' state over the second walk: the two columns left of
+// c and the sums of the per-column rows (nothing in the base set)
+template <bool EXT>
+struct ExtAcc {};
+template <>
+struct ExtAcc<true> {
+    uint32_t w1, w2, hole_or = 0;
+    int32_t rtr = 0, ctr = 0, wells = 0, hdepth = 0;
+};
+
+template <int SET, class ColOut>
+__device__ __forceinline__ bool eval_slot_set(const uint32_t *C, int W, int H, uint32_t flags, int id, int s,
+                                              int32_t old_holes, int32_t old_height,
+                                              int32_t (&f)[feat_rows(SET)], ColOut col_out) {
+    constexpr bool EXT = SET == ST_FEATS_BCTS;
+    const uint32_t hmask = (1u << H) - 1u, floorb = ~hmask;
+    const int per = W + 6;
+    const int r = (s >= per) + (s >= 2 * per) + (s >= 3 * per), x = s - r * per - 3;
+    const uint32_t m = c_tab_m[id * 4 + r], g = c_tab_g[id * 4 + r];
+    const int x0 = box_x0(g, x);
+    uint32_t v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = C[x0 + j];
+    const bool valid = !collides_v(m, 0, v);
+    const int y = valid ? drop_box(g, 0, v) : 0;
+    bool above = false;
+    uint32_t pb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t byte = (m >> (8 * j)) & 0xFFu;
+        above = above || (byte != 0u && y + __builtin_ctz(byte) - 3 < 0);  // (a box column without cells)
+        pb[j] = pc_bits(m, j, y) & hmask;
+    }
+    // the board with the piece: column c gets the bits of the box column at c
+    uint32_t andv = hmask;
+    for (int c = 0; c < W; ++c) {
+        uint32_t w = C[c];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
+        andv &= w;
+    }
+    const int32_t ncl = __builtin_popcount(andv);
+    int32_t holes = 0, agg = 0, bump = 0, hprev = 0;
+    uint32_t orv = 0;
+    ExtAcc<EXT> x_;
+    if constexpr (EXT) x_.w1 = x_.w2 = hmask;  // the left wall
+    for (int c = 0; c < W; ++c) {
+        uint32_t w = C[c] & hmask;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
+        if (andv) w = compact(w, andv);
+        if constexpr (EXT) {
+            x_.rtr += __builtin_popcount(x_.w1 ^ w);
+            const uint32_t wf = w | (1u << H);  // the floor counts as filled
+            x_.ctr += __builtin_popcount((wf ^ (wf >> 1)) & hmask);
+            if (c) x_.wells += well_sum(~x_.w1 & x_.w2 & w & hmask);  // column c - 1
+            const uint32_t top = w & (0u - w);                // the column's topmost cell (0: none)
+            uint32_t hl = ~w & hmask & ~(top | (top - 1u));   // its holes: empty, below the top
+            x_.hole_or |= hl;
+            while (hl) {
+                x_.hdepth += __builtin_popcount(w & ((hl & (0u - hl)) - 1u));  // the cells above this hole
+                hl &= hl - 1u;
+            }
+            x_.w2 = x_.w1;
+            x_.w1 = w;
+        }
+        const int32_t h = H - (int32_t)__builtin_ctz(w | floorb);  // the column's height
+        holes += h - __builtin_popcount(w);
+        agg += h;
+        bump += c ? (h > hprev ? h - hprev : hprev - h) : 0;
+        hprev = h;
+        orv |= w;
+        col_out(c, w, valid);
+    }
+    int32_t rew = (flags & ST_REWARD_STEP) ? 1 : 0;  // :256
+    int32_t score = 0, lines = 0, nholes = 0, height = 0, deaths = 0;
+    lock_score<false>(flags, ncl, orv, [&] { return holes; }, old_holes, old_height, rew, score, lines, nholes, height,
+                      deaths);
+    f[ST_AFTER_VALID] = 1;
+    f[ST_AFTER_Y] = y;
+    f[ST_AFTER_LINES] = ncl;
+    f[ST_AFTER_HOLES] = holes;
+    f[ST_AFTER_HEIGHT] = orv ? H - (int32_t)__builtin_ctz(orv) : 0;
+    f[ST_AFTER_ROWS] = __builtin_popcount(orv);
+    f[ST_AFTER_ABOVE] = above ? 1 : 0;
+    f[ST_AFTER_DEAD] = (int32_t)(orv & 1u);
+    f[ST_AFTER_REWARD] = rew;
+    f[ST_AFTER_AGG_HEIGHT] = agg;
+    f[ST_AFTER_BUMPINESS] = bump;
+    if constexpr (EXT) {
+        x_.rtr += __builtin_popcount(x_.w1 ^ hmask);    // the last column against the right wall
+        x_.wells += well_sum(~x_.w1 & x_.w2 & hmask);   // column W - 1 (W >= 4: w2 is column W - 2)
+        // the rows the piece spans, unclipped: bit dy + 3 of a box byte is row y + dy
+        const uint32_t span = (m | m >> 8 | m >> 16 | m >> 24) & 0xFFu;
+        const int32_t ymin = y + (int32_t)__builtin_ctz(span) - 3, ymax = y + 28 - (int32_t)__builtin_clz(span);
+        int32_t gone = 0;  // cells of the piece, inside the board, in a row that was cleared
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gone += __builtin_popcount(pb[j] & andv);
+        f[ST_AFTER_NFEAT + ST_AFTER_EXT_LANDING2] = 2 * H - 1 - (ymin + ymax);
+        f[ST_AFTER_NFEAT + ST_AFTER_EXT_ERODED] = ncl * gone;
+        f[ST_AFTER_NFEAT + ST_AFTER_EXT_ROW_TRANS] = x_.rtr;
+        f[ST_AFTER_NFEAT + ST_AFTER_EXT_COL_TRANS] = x_.ctr;
+        f[ST_AFTER_NFEAT + ST_AFTER_EXT_WELLS] = x_.wells;
+        f[ST_AFTER_NFEAT + ST_AFTER_EXT_HOLE_DEPTH] = x_.hdepth;
+        f[ST_AFTER_NFEAT + ST_AFTER_EXT_HOLE_ROWS] = __builtin_popcount(x_.hole_or);
+    }
+    return valid;
+}
+#endif  // ST_EVAL_TU
+
+#if defined(ST_EVAL_TU) || defined(ST_REACHABLE_TU)
 // The wave's W + 2 * P column words (floor bits, all-ones walls): lanes
 // 0 .. W + 2 * P - 1 write one word each.
 constexpr int kAfterP = 8;  // wall columns each side: the box's columns span [-6, W + 5]
@@ -3999,8 +4137,9 @@ __device__ __forceinline__ void stage_env_columns(uint32_t *L, const KParams &p,
 }
 #endif
 
-#ifdef ST_AFTERSTATES_TU
+#ifdef ST_EVAL_TU
 
+#ifdef ST_AFTERSTATES_TU
 __global__ __launch_bounds__(kWave) void k_afterstates(KParams p, int32_t *__restrict__ feat,
                                                        uint32_t *__restrict__ boards) {
     __shared__ uint32_t L[kAfterCols];
@@ -4031,7 +4170,43 @@ __global__ __launch_bounds__(kWave) void k_afterstates(KParams p, int32_t *__res
         }
     }
 }
+#else
+// k_afterstates with the rows of SET: feat [n][feat_rows(SET)][S]
+template <int SET>
+__global__ __launch_bounds__(kWave) void k_afterstates_set(KParams p, int32_t *__restrict__ feat,
+                                                           uint32_t *__restrict__ boards) {
+    constexpr int NF = feat_rows(SET);
+    __shared__ uint32_t L[kAfterCols];
+    const int lane = threadIdx.x;
+    const int64_t e = blockIdx.x;  // the grid is p.n waves: padding envs are not evaluated
+    const int64_t sd = p.stride;
+    const int W = p.W, H = p.H;
+    const int S = 4 * (W + 6);
+    stage_env_columns(L, p, e, lane);
+    const uint32_t pid = p.piece[e] & 7u;
+    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
+    const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
+    const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd + e];
+    wave_sync();
+    const size_t fbase = (size_t)e * NF * S, bbase = (size_t)e * W * S;
+    for (int s0 = 0; s0 < S; s0 += kWave) {
+        const int s = s0 + lane;
+        const bool live = s < S;
+        const int sc = live ? s : S - 1;  // (lanes past the last slot compute it again, store nothing)
+        int32_t f[NF];
+        const bool valid = eval_slot_set<SET>(L + kAfterP, W, H, p.flags, id, sc, old_holes, old_height, f,
+                                          [&](int c, uint32_t w, bool ok) {
+                                              if (boards && live) boards[bbase + (size_t)c * S + s] = ok ? w : 0u;
+                                          });
+        if (live) {
+#pragma unroll
+            for (int row = 0; row < NF; ++row) feat[fbase + (size_t)row * S + s] = valid ? f[row] : 0;
+        }
+    }
+}
+#endif
 
+#ifdef ST_AFTERSTATES_TU
 // st_placement_actions: the primitive action that moves env e's live piece
 // toward slot slots[e] -- k_policy_greedy's rule (gen_golden.greedy_action):
 // rotate_left until the rotation matches, then move toward x, then hard-drop;
@@ -4051,6 +4226,7 @@ __global__ __launch_bounds__(256) void k_placement_actions(KParams p, const int3
     }
     out[e] = (uint8_t)a;
 }
+#endif  // ST_AFTERSTATES_TU
 
 // ---------------------------------------------------------------- placement step
 // st_place: commit slot slots[e] of env e (simpletetris.h, "Placement step").
@@ -4067,6 +4243,7 @@ __device__ __forceinline__ uint32_t placed_piece(int id, int rot, int x, int loc
     return (uint32_t)id | (uint32_t)rot << 3 | (uint32_t)x << 5 | (uint32_t)(lock_mod - 1) << 17;  // anchor row 0
 }
 
+#ifdef ST_AFTERSTATES_TU
 // One lane per env: the piece word, the slot and the slot's four box columns
 // (floor bits, all-ones walls outside [0, W), as stage_env_columns gives them)
 // are the lane's only loads; the piece word leaves with a plain vector store.
@@ -4095,6 +4272,7 @@ __global__ __launch_bounds__(256) void k_place(KParams p, const int32_t *__restr
     }
     if (placed) placed[e] = ok ? 1 : 0;
 }
+#endif  // ST_AFTERSTATES_TU
 
 // ---------------------------------------------------------------- linear feature player
 // st_policy_linear: env e scores every slot of its current piece with weight
@@ -4127,6 +4305,7 @@ __global__ __launch_bounds__(256) void k_place(KParams p, const int32_t *__restr
 // a ring's worth at a time -- one lane per env, whole cache lines.  (Adding
 // in this kernel, one lane per wave or one wave per 64 envs, measured 3.8 /
 // 1.5 us per step at 65,536 envs.)
+#ifdef ST_AFTERSTATES_TU
 __global__ __launch_bounds__(256) void k_play_sum(const int32_t *__restrict__ reward, const uint8_t *__restrict__ done,
                                                   int rows, int64_t n, int64_t *__restrict__ ret,
                                                   int32_t *__restrict__ episodes, int32_t *__restrict__ out_reward,
@@ -4145,12 +4324,14 @@ __global__ __launch_bounds__(256) void k_play_sum(const int32_t *__restrict__ re
     if (out_reward) out_reward[e] = reward[(int64_t)(rows - 1) * n + e];
     if (out_done) out_done[e] = done[(int64_t)(rows - 1) * n + e];
 }
+#endif  // ST_AFTERSTATES_TU
 
-__device__ __forceinline__ float lin_score(const float (&w)[ST_AFTER_NFEAT], const int32_t (&f)[ST_AFTER_NFEAT]) {
+template <int NF>
+__device__ __forceinline__ float lin_score(const float (&w)[NF], const int32_t (&f)[NF]) {
 #pragma clang fp contract(off)
     float acc = 0.0f;
 #pragma unroll
-    for (int r = 0; r < ST_AFTER_NFEAT; ++r) {
+    for (int r = 0; r < NF; ++r) {
         float prod = w[r] * (float)f[r];
         asm volatile("" : "+v"(prod));  // the rounded product, opaque to the add below
         acc = acc + prod;
@@ -4190,6 +4371,7 @@ struct PassTag {
 // COMMIT (st_play_linear_placements): the lane that writes the env's outputs
 // also stores the chosen slot's piece word (placed_piece: k_place's commit,
 // without its launch); it stores nothing if no slot is valid.
+#ifdef ST_AFTERSTATES_TU
 template <int WAVES, bool COMMIT = false>
 __global__ __launch_bounds__(WAVES *kWave) void k_policy_linear(KParams p, const float *__restrict__ wts, int64_t n_w,
                                                                 int32_t *__restrict__ slots,
@@ -4275,7 +4457,101 @@ __global__ __launch_bounds__(WAVES *kWave) void k_policy_linear(KParams p, const
         }
     }
 }
-#endif  // ST_AFTERSTATES_TU
+#else
+// k_policy_linear over the rows of SET (weights [n_w][NF], best [NF][n]) and
+// with a slot mask: allowed int32 [n][S] or null; a slot is a candidate iff it
+// is valid and its word is not 0.
+template <int WAVES, bool COMMIT, int SET>
+__global__ __launch_bounds__(WAVES *kWave) void k_policy_linear_set(KParams p, const float *__restrict__ wts,
+                                                                    int64_t n_w, const int32_t *__restrict__ allowed,
+                                                                    int32_t *__restrict__ slots,
+                                                                    uint8_t *__restrict__ actions,
+                                                                    float *__restrict__ scores,
+                                                                    int32_t *__restrict__ best) {
+    __shared__ uint32_t Lall[WAVES * kAfterCols];
+    constexpr int NF = feat_rows(SET);
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t e = (int64_t)blockIdx.x * WAVES + wave;
+    if (e >= p.n) return;  // (wave-uniform; the kernel has no workgroup barrier)
+    uint32_t *L = Lall + wave * kAfterCols;
+    const int64_t sd = p.stride;
+    const int W = p.W, H = p.H;
+    const int per = W + 6, S = 4 * per;
+    stage_env_columns(L, p, e, lane);
+    const uint32_t pw = p.piece[e];
+    const uint32_t pid = pw & 7u;
+    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
+    const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
+    const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd + e];
+    // e < 2^24 (st_create), so the row index is 32-bit arithmetic
+    const uint32_t wrow = n_w > e ? (uint32_t)e : (uint32_t)e % (uint32_t)n_w;
+    float w[NF];
+#pragma unroll
+    for (int r = 0; r < NF; ++r) w[r] = wts[(size_t)wrow * NF + r];
+    wave_sync();
+    // the lane's candidate: its best slot so far (-1: none), that slot's score and rows
+    int32_t bslot;
+    float bscore;
+    int32_t bf[NF];
+    auto pass = [&](int s0, auto first) {
+        const int s = s0 + lane;
+        const bool live = s < S;
+        int32_t f[NF];
+        bool valid = eval_slot_set<SET>(L + kAfterP, W, H, p.flags, id, live ? s : S - 1, old_holes, old_height, f,
+                                    [](int, uint32_t, bool) {});
+        // (a slot the mask refuses is no candidate: from here on, as if invalid)
+        if (allowed) valid = valid && live && allowed[(size_t)e * S + s] != 0;
+        const float sc = lin_score(w, f);
+        if constexpr (decltype(first)::value) {  // (score and rows are read only where bslot >= 0)
+            bslot = live && valid ? s : -1;
+            bscore = sc;
+#pragma unroll
+            for (int r = 0; r < NF; ++r) bf[r] = f[r];
+        } else if (live && valid && (bslot < 0 || sc > bscore)) {
+            bslot = s;
+            bscore = sc;
+#pragma unroll
+            for (int r = 0; r < NF; ++r) bf[r] = f[r];
+        }
+    };
+    pass(0, PassTag<true>{});
+    for (int s0 = kWave; s0 < S; s0 += kWave) pass(s0, PassTag<false>{});
+    // the wave's maximum over the candidates, then the lowest slot that reaches
+    // it.  With finite weights some candidate equals the maximum; a NaN score
+    // equals nothing, and then every candidate counts as reaching it, so that
+    // the slot stays a valid one.
+    const bool has = bslot >= 0;
+    const float top = __int_as_float(wave_reduce(__float_as_int(has ? bscore : -__builtin_inff()), [](int a, int b) {
+        return __float_as_int(__builtin_fmaxf(__int_as_float(a), __int_as_float(b)));
+    }));
+    bool tied = has && bscore == top;
+    if (__ballot(tied) == 0) tied = has;
+    const int32_t win = wave_reduce(tied ? bslot : INT32_MAX, [](int a, int b) { return a < b ? a : b; });
+    const bool none = win == INT32_MAX;  // no valid slot: lane 0 writes slot -1, action 2, score 0, zero rows
+    if (none ? lane == 0 : tied && bslot == win) {
+        if (slots) slots[e] = none ? -1 : win;
+        if (scores) scores[e] = none ? 0.0f : bscore;
+        if (actions) {
+            const int rot = (int)((pw >> 3) & 3u), ax = (int)((pw >> 5) & 63u);
+            const int trot = (win >= per) + (win >= 2 * per) + (win >= 3 * per), tx = win - trot * per - 3;
+            // k_placement_actions's rule
+            actions[e] = (uint8_t)(none ? 2u : rot != trot ? 4u : (ax < tx ? 1u : (ax > tx ? 0u : 2u)));
+        }
+        if (best) {
+#pragma unroll
+            for (int r = 0; r < NF; ++r) best[(size_t)r * p.n + e] = none ? 0 : bf[r];
+        }
+        if constexpr (COMMIT) {
+            if (!none) {
+                const int trot = (win >= per) + (win >= 2 * per) + (win >= 3 * per), tx = win - trot * per - 3;
+                p.piece[e] = placed_piece(id, trot, tx, p.lock_mod);
+            }
+        }
+    }
+}
+#endif
+#endif  // ST_EVAL_TU
 
 #ifdef ST_REACHABLE_TU
 // ---------------------------------------------------------------- reachability
@@ -4536,6 +4812,30 @@ hipError_t launch_play_sum(const KParams &p, const int32_t *reward, const uint8_
                            int32_t *acc_episodes, int32_t *out_reward, uint8_t *out_done, hipStream_t s) {
     hipLaunchKernelGGL(k_play_sum, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, reward, done, rows, p.n,
                        acc_return, acc_episodes, out_reward, out_done);
+    return hipGetLastError();
+}
+#elif defined(ST_FEATURES_TU)
+hipError_t launch_afterstates_set(const KParams &p, int set, int32_t *feat, uint32_t *boards, hipStream_t s) {
+    if (set != ST_FEATS_BCTS) return hipErrorInvalidValue;  // (the base set is launch_afterstates)
+    hipLaunchKernelGGL((k_afterstates_set<ST_FEATS_BCTS>), dim3((unsigned)p.n), dim3(kWave), 0, s, p, feat, boards);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_linear_set(const KParams &p, int set, bool commit, const float *weights, int64_t n_w,
+                                    const int32_t *allowed, int32_t *slots, uint8_t *actions, float *scores,
+                                    int32_t *best, hipStream_t s) {
+    constexpr int WV = ST_POLICY_WAVES;
+    const dim3 grid((unsigned)((p.n + WV - 1) / WV)), block(WV * kWave);
+#define ST_PL_ARGS p, weights, n_w, allowed, slots, actions, scores, best
+    if (set == ST_FEATS_BCTS && commit)
+        hipLaunchKernelGGL((k_policy_linear_set<WV, true, ST_FEATS_BCTS>), grid, block, 0, s, ST_PL_ARGS);
+    else if (set == ST_FEATS_BCTS)
+        hipLaunchKernelGGL((k_policy_linear_set<WV, false, ST_FEATS_BCTS>), grid, block, 0, s, ST_PL_ARGS);
+    else if (set == ST_FEATS_BASE && !commit)  // (the base set without a mask is launch_policy_linear)
+        hipLaunchKernelGGL((k_policy_linear_set<WV, false, ST_FEATS_BASE>), grid, block, 0, s, ST_PL_ARGS);
+    else
+        return hipErrorInvalidValue;
+#undef ST_PL_ARGS
     return hipGetLastError();
 }
 #elif defined(ST_REACHABLE_TU)

@@ -43,6 +43,11 @@ EXPORT_MT, EXPORT_OBS_F32 = 1, 2  # st_export_env parts
 AFTER = dict(valid=0, y=1, lines=2, holes=3, height=4, rows=5, above=6, dead=7, reward=8, agg_height=9,
              bumpiness=10)
 AFTER_NFEAT = 11
+# st_after_ext: the rows ST_FEATS_BCTS adds behind AFTER's, by name -> extended row index
+AFTER_EXT = dict(landing2=11, eroded=12, row_trans=13, col_trans=14, wells=15, hole_depth=16, hole_rows=17)
+AFTER_BCTS = {**AFTER, **AFTER_EXT}  # the 18 rows of ST_FEATS_BCTS, in row order
+FEATURE_SETS = dict(base=0, bcts=1)  # st_feature_set
+FEATURE_NAMES = {"base": AFTER, "bcts": AFTER_BCTS}  # feature set -> its rows by name
 REACH_MAX_LOCK = 3  # ST_REACH_MAX_LOCK: the largest lock_delay st_reachable / st_route_actions take
 
 
@@ -115,6 +120,10 @@ SIG = {
     "st_place": ([_vp, _vp, _vp, _vp], ctypes.c_int),
     "st_step_placements": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_play_linear_placements": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_feature_rows": ([_i32], ctypes.c_int),
+    "st_afterstates_set": ([_vp, _i32, _vp, _vp, _vp], ctypes.c_int),
+    "st_policy_linear_set": ([_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_play_linear_set": ([_vp, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_debug_stamps": ([_vp, _vp, _i64], ctypes.c_int),
     "st_last_error": ([], ctypes.c_char_p),
     "st_abi_version": ([], ctypes.c_int),
@@ -149,7 +158,7 @@ def load(path: str = LIB_PATH):
             if ab_override:
                 continue
             # an addition that did not change the ABI number (st_step_export, st_afterstates,
-            # st_policy_linear, st_place, st_reachable):
+            # st_policy_linear, st_place, st_reachable, st_afterstates_set):
             # the library on disk was built before it
             raise ImportError(f"{path}: no symbol {name} (a stale build of ABI {abi}: rebuild it with "
                               "`make -C gym-simpletetris_amd/csrc`)")

@@ -161,16 +161,31 @@ def placement_rot_x(width: int, slot: int):
     return slot // (width + 6), slot % (width + 6) - 3
 
 
+def _row_names(rows: int):
+    """The rows by name of a feature tensor with `rows` rows: _lib.AFTER, or
+    _lib.AFTER_BCTS where it holds the 18 rows of features='bcts'."""
+    return C.AFTER_BCTS if rows == len(C.AFTER_BCTS) else C.AFTER
+
+
+def _feature_set(features):
+    """(st_feature_set value, rows, rows by name) of a `features` argument."""
+    if not isinstance(features, str) or features not in C.FEATURE_SETS:
+        raise ValueError(f"features must be one of {', '.join(map(repr, C.FEATURE_SETS))}, got {features!r}")
+    names = C.FEATURE_NAMES[features]
+    return C.FEATURE_SETS[features], len(names), names
+
+
 class Afterstates:
-    """TetrisBatch.afterstates()'s result: `feat` int32 [n, AFTER_NFEAT, S] and
-    `boards` int32 [n, W, S] (or None), slot innermost; every feature row by
-    its name in _lib.AFTER as an [n, S] view of feat (.valid, .lines, ...)."""
+    """TetrisBatch.afterstates()'s result: `feat` int32 [n, rows, S] (rows =
+    AFTER_NFEAT, or 18 with features='bcts') and `boards` int32 [n, W, S] (or
+    None), slot innermost; every feature row by its name in _lib.AFTER (with 18
+    rows: _lib.AFTER_BCTS) as an [n, S] view of feat (.valid, .lines, ...)."""
 
     def __init__(self, feat: torch.Tensor, boards: Optional[torch.Tensor]):
         self.feat, self.boards = feat, boards
 
     def __getattr__(self, name):  # (only names not found otherwise)
-        row = C.AFTER.get(name)
+        row = _row_names(self.feat.shape[1]).get(name) if name != "feat" else None
         if row is None:
             raise AttributeError(name)
         return self.feat[:, row]
@@ -194,25 +209,37 @@ class Reachable:
 # st_policy_greedy's score as linear feature weights: 80 * lines - 12 * holes
 # - 3 * height - 2000 * above (rows by their names in _lib.AFTER)
 GREEDY_WEIGHTS = MappingProxyType(dict(lines=80.0, holes=-12.0, height=-3.0, above=-2000.0))
+# Dellacherie's six-feature player and Thiery & Scherrer's BCTS player as weights over
+# the rows of features='bcts' (_lib.AFTER_BCTS).  The published landing-height weight
+# (-1 / -12.63) is halved, since the row `landing2` is twice the landing height.  The
+# values were written down from memory of the published tables, not copied from the
+# papers: check them against the sources before quoting results obtained with them.
+DELLACHERIE_WEIGHTS = MappingProxyType(dict(landing2=-0.5, eroded=1.0, row_trans=-1.0, col_trans=-1.0, holes=-4.0,
+                                            wells=-1.0))
+BCTS_WEIGHTS = MappingProxyType(dict(landing2=-6.315, eroded=6.60, row_trans=-9.22, col_trans=-19.77, holes=-13.08,
+                                     wells=-10.49, hole_depth=-1.61, hole_rows=-24.04))
 
 
-def weight_rows(weights) -> np.ndarray:
-    """Host weights for policy_linear / play_linear as float32 [n_w, AFTER_NFEAT]:
-    a mapping by _lib.AFTER name (missing names are 0; the header's enum order
-    places the values), a sequence of AFTER_NFEAT numbers, or a sequence of
-    such mappings / sequences (one row per candidate)."""
+def weight_rows(weights, features: str = "base") -> np.ndarray:
+    """Host weights for policy_linear / play_linear as float32 [n_w, rows], rows =
+    AFTER_NFEAT (features='bcts': 18): a mapping by the set's row names
+    (_lib.AFTER / _lib.AFTER_BCTS; missing names are 0; the header's enum order
+    places the values), a sequence of `rows` numbers, or a sequence of such
+    mappings / sequences (one row per candidate)."""
+    _, nrows, names = _feature_set(features)
+
     def row(w):
         if isinstance(w, Mapping):
-            unknown = sorted(set(w) - set(C.AFTER))
+            unknown = sorted(set(w) - set(names))
             if unknown:
-                raise ValueError(f"weights: no feature row named {unknown[0]!r} (rows: {', '.join(C.AFTER)})")
-            v = np.zeros(C.AFTER_NFEAT, np.float32)
+                raise ValueError(f"weights: no feature row named {unknown[0]!r} (rows: {', '.join(names)})")
+            v = np.zeros(nrows, np.float32)
             for name, val in w.items():
-                v[C.AFTER[name]] = val
+                v[names[name]] = val
             return v
         w = np.asarray(w)
-        if w.shape != (C.AFTER_NFEAT,):
-            raise ValueError(f"weights: a row needs {C.AFTER_NFEAT} values, got shape {w.shape}")
+        if w.shape != (nrows,):
+            raise ValueError(f"weights: a row needs {nrows} values, got shape {w.shape}")
         return w
     if isinstance(weights, Mapping):
         out = row(weights)
@@ -226,26 +253,28 @@ def weight_rows(weights) -> np.ndarray:
         raise TypeError(f"weights must be real numbers, got {out.dtype}")
     out = out.astype(np.float32)
     out = out[None] if out.ndim == 1 else out
-    if out.ndim != 2 or out.shape[1] != C.AFTER_NFEAT or out.shape[0] < 1:
-        raise ValueError(f"weights: need [{C.AFTER_NFEAT}] or [n_w, {C.AFTER_NFEAT}] values, got shape {np.shape(weights)}")
+    if out.ndim != 2 or out.shape[1] != nrows or out.shape[0] < 1:
+        raise ValueError(f"weights: need [{nrows}] or [n_w, {nrows}] values, got shape {np.shape(weights)}")
     return np.ascontiguousarray(out)
 
 
 class LinearChoice:
     """TetrisBatch.policy_linear()'s result: `slots` int32 [n] (-1: no valid
     slot), `actions` uint8 [n] (as step() takes them), `scores` float32 [n] and
-    `feat` int32 [AFTER_NFEAT, n], the chosen slot's feature rows with the env
-    innermost; every row by its name in _lib.AFTER as an [n] view of feat
-    (.lines, .holes, ...).  A field not asked for (`out`) is None."""
+    `feat` int32 [rows, n] (rows = AFTER_NFEAT, or 18 with features='bcts'), the
+    chosen slot's feature rows with the env innermost; every row by its name in
+    _lib.AFTER (with 18 rows: _lib.AFTER_BCTS) as an [n] view of feat (.lines,
+    .holes, ...).  A field not asked for (`out`) is None."""
 
     def __init__(self, slots, actions, scores, feat):
         self.slots, self.actions, self.scores, self.feat = slots, actions, scores, feat
 
     def __getattr__(self, name):  # (only names not found otherwise)
-        row = C.AFTER.get(name)
-        if row is None or self.feat is None:
+        feat = None if name == "feat" else self.feat
+        row = None if feat is None else _row_names(feat.shape[0]).get(name)
+        if row is None:
             raise AttributeError(name)
-        return self.feat[row]
+        return feat[row]
 
 
 class TetrisBatch:
@@ -757,7 +786,7 @@ class TetrisBatch:
     def slot_rot_x(self, slot: int):
         return placement_rot_x(self.width, slot)
 
-    def afterstates(self, boards: bool = True, out=None) -> Afterstates:
+    def afterstates(self, boards: bool = True, out=None, features: str = "base") -> Afterstates:
         """Every placement of every env's current piece, in one launch
         (st_afterstates): slot s = slot(rot, x) is the piece in rotation rot
         at anchor (x, 0), valid iff not is_occupied there (tetris_env.py:29-36),
@@ -771,19 +800,28 @@ class TetrisBatch:
         greedy policy scores: no promise that moves, rotations and gravity can
         bring the live piece there.  Reads the state, changes none of it.
         `out`: a (feat, boards) pair of device tensors to write (boards None
-        without `boards`)."""
+        without `boards`).
+        features='bcts' (st_afterstates_set) gives feat int32 [n, 18, S]: the
+        eleven rows, then .landing2, .eroded, .row_trans, .col_trans, .wells,
+        .hole_depth, .hole_rows (_lib.AFTER_EXT; simpletetris.h, "Feature
+        sets") -- the rows of Dellacherie's and the BCTS players; the boards
+        are the same."""
         n, W, S = self.n, self.width, self.n_slots
+        fset, nrows, _ = _feature_set(features)
         if out is None:
-            feat = torch.empty((n, C.AFTER_NFEAT, S), dtype=torch.int32, device=self.device)
+            feat = torch.empty((n, nrows, S), dtype=torch.int32, device=self.device)
             brd = torch.empty((n, W, S), dtype=torch.int32, device=self.device) if boards else None
         else:
             feat, brd = out
-            _check_tensor(feat, "out feat", (n, C.AFTER_NFEAT, S), (torch.int32,), self.device)
+            _check_tensor(feat, "out feat", (n, nrows, S), (torch.int32,), self.device)
             if boards:
                 _check_tensor(brd, "out boards", (n, W, S), (torch.int32,), self.device)
             elif brd is not None:
                 raise ValueError("out boards given with boards=False")
-        C.check(self._L.st_afterstates(self._ctx, _ptr(feat), _ptr(brd), self._stream()))
+        if features == "base":
+            C.check(self._L.st_afterstates(self._ctx, _ptr(feat), _ptr(brd), self._stream()))
+        else:
+            C.check(self._L.st_afterstates_set(self._ctx, fset, _ptr(feat), _ptr(brd), self._stream()))
         return Afterstates(feat, brd)
 
     def _slots(self, slots) -> torch.Tensor:
@@ -914,19 +952,21 @@ class TetrisBatch:
         return o_ret, r_t, d_t
 
     # ------------------------------------------------------------ linear feature players
-    def _weights(self, weights) -> torch.Tensor:
+    def _weights(self, weights, features: str = "base") -> torch.Tensor:
         """policy_linear's / play_linear's weights as a float32 device tensor
-        [n_w, AFTER_NFEAT]: a device tensor [AFTER_NFEAT] or [n_w, AFTER_NFEAT]
-        as it is (checked, never converted), anything else through weight_rows."""
+        [n_w, rows] (rows = AFTER_NFEAT, features='bcts': 18): a device tensor
+        [rows] or [n_w, rows] as it is (checked, never converted), anything
+        else through weight_rows."""
+        nrows = _feature_set(features)[1]
         if isinstance(weights, torch.Tensor):
             w = weights[None] if weights.dim() == 1 else weights
-            _check_tensor(w, "weights", (None, C.AFTER_NFEAT), (torch.float32,), self.device)
+            _check_tensor(w, "weights", (None, nrows), (torch.float32,), self.device)
             if w.shape[0] < 1:
                 raise ValueError("weights: no rows")
             return w
-        return torch.as_tensor(weight_rows(weights), device=self.device)
+        return torch.as_tensor(weight_rows(weights, features), device=self.device)
 
-    def policy_linear(self, weights, out=None) -> LinearChoice:
+    def policy_linear(self, weights, out=None, features: str = "base", allowed=None) -> LinearChoice:
         """Every env's best placement under linear feature weights, in one
         launch (st_policy_linear).  Env e scores every placement slot of its
         current piece -- afterstates()'s slots and feature rows -- with weight
@@ -941,31 +981,48 @@ class TetrisBatch:
         placement_actions gives for the slot), .scores, .feat [AFTER_NFEAT, n]
         and its rows by name.  Reads the state, changes none of it.
         `out`: a (slots, actions, scores, feat) tuple of device tensors to
-        write; None entries are not computed (at least one must be given)."""
+        write; None entries are not computed (at least one must be given).
+        features='bcts' (st_policy_linear_set) scores the 18 rows of
+        afterstates(features='bcts') -- weights [18] / [n_w, 18] or a dict by
+        _lib.AFTER_BCTS name (DELLACHERIE_WEIGHTS, BCTS_WEIGHTS), .feat [18, n].
+        allowed: a slot mask, a Reachable (its .steps) or an int32 [n, S] device
+        tensor: only valid slots whose entry is not 0 are candidates -- with
+        reachable() the player is confined to the slots the live piece can
+        really reach; where none is left: slot -1, action 2, score 0."""
         n = self.n
-        w = self._weights(weights)
+        fset, nrows, _ = _feature_set(features)
+        w = self._weights(weights, features)
+        if isinstance(allowed, Reachable):
+            allowed = allowed.steps
+        if allowed is not None:
+            _check_tensor(allowed, "allowed", (n, self.n_slots), (torch.int32,), self.device)
         if out is None:
             out = (torch.empty(n, dtype=torch.int32, device=self.device),
                    torch.empty(n, dtype=torch.uint8, device=self.device),
                    torch.empty(n, dtype=torch.float32, device=self.device),
-                   torch.empty((C.AFTER_NFEAT, n), dtype=torch.int32, device=self.device))
+                   torch.empty((nrows, n), dtype=torch.int32, device=self.device))
         else:
             if not isinstance(out, (tuple, list)) or len(out) != 4:
                 raise ValueError("out: a (slots, actions, scores, feat) tuple, None for an output not wanted")
             if all(t is None for t in out):
                 raise ValueError("out: at least one output tensor is needed")
             for t, name, shape, dt in zip(out, ("slots", "actions", "scores", "feat"),
-                                          ((n,), (n,), (n,), (C.AFTER_NFEAT, n)),
+                                          ((n,), (n,), (n,), (nrows, n)),
                                           (torch.int32, torch.uint8, torch.float32, torch.int32)):
                 if t is not None:
                     _check_tensor(t, "out " + name, shape, (dt,), self.device)
         sl, ac, sc, ft = out
-        C.check(self._L.st_policy_linear(self._ctx, _ptr(w), w.shape[0], _ptr(sl), _ptr(ac), _ptr(sc), _ptr(ft),
-                                         self._stream()))
+        if features == "base" and allowed is None:
+            C.check(self._L.st_policy_linear(self._ctx, _ptr(w), w.shape[0], _ptr(sl), _ptr(ac), _ptr(sc), _ptr(ft),
+                                             self._stream()))
+        else:
+            C.check(self._L.st_policy_linear_set(self._ctx, fset, _ptr(w), w.shape[0], _ptr(allowed), _ptr(sl),
+                                                 _ptr(ac), _ptr(sc), _ptr(ft), self._stream()))
         return LinearChoice(sl, ac, sc, ft)
 
     def play_linear(self, weights, k: int, returns: Optional[torch.Tensor] = None,
-                    episodes: Optional[torch.Tensor] = None, obs: str = "none", placements: bool = False):
+                    episodes: Optional[torch.Tensor] = None, obs: str = "none", placements: bool = False,
+                    features: str = "base"):
         """k steps of policy_linear(weights) -> step, enqueued by ONE library
         call (st_play_linear: no Python, no host read-back between the steps),
         identical to k rounds of policy_linear + step by hand.  Adds every
@@ -984,12 +1041,15 @@ class TetrisBatch:
         k rounds of policy_linear -> step_placements(its slots), the policy's
         launch committing its own choice -- every iteration locks a piece
         (where a slot is valid) and pays exactly the afterstate reward the
-        policy maximised; two launches per piece."""
+        policy maximised; two launches per piece.
+        features='bcts' (st_play_linear_set) plays with the 18 rows of
+        policy_linear(features='bcts'), at either level."""
         if obs not in ("packed", "none"):
             raise ValueError("obs must be 'packed' or 'none'")
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
             raise ValueError(f"k must be an integer >= 0, got {k!r}")
-        w = self._weights(weights)
+        fset = _feature_set(features)[0]
+        w = self._weights(weights, features)
         if returns is None:
             returns = torch.zeros(self.n, dtype=torch.int64, device=self.device)
         else:
@@ -998,9 +1058,14 @@ class TetrisBatch:
             episodes = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         else:
             _check_tensor(episodes, "episodes", (self.n,), (torch.int32,), self.device)
-        fn = self._L.st_play_linear_placements if placements else self._L.st_play_linear
-        C.check(fn(self._ctx, _ptr(w), w.shape[0], int(k), _ptr(returns), _ptr(episodes),
-                 _ptr(self.obs) if obs == "packed" else None, _ptr(self.reward), _ptr(self.done), self._stream()))
+        tail = (_ptr(returns), _ptr(episodes), _ptr(self.obs) if obs == "packed" else None, _ptr(self.reward),
+                _ptr(self.done), self._stream())
+        if features == "base":
+            fn = self._L.st_play_linear_placements if placements else self._L.st_play_linear
+            C.check(fn(self._ctx, _ptr(w), w.shape[0], int(k), *tail))
+        else:
+            C.check(self._L.st_play_linear_set(self._ctx, fset, _ptr(w), w.shape[0], int(k), int(bool(placements)),
+                                               *tail))
         return returns, episodes
 
 

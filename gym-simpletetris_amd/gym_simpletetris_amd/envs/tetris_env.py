@@ -534,32 +534,34 @@ class TetrisVecEnv:
         reached any step so far (waits for the queued work)."""
         self.engine.check_actions()
 
-    def afterstates(self, boards: bool = True, out=None):
+    def afterstates(self, boards: bool = True, out=None, features="base"):
         """TetrisBatch.afterstates of the engine, on its stream: every
         placement of every env's current piece (features and boards), for an
         afterstate agent's afterstates -> score -> argmax ->
-        placement_actions -> step loop."""
-        return self.engine.afterstates(boards=boards, out=out)
+        placement_actions -> step loop.  features='bcts': the 18 rows."""
+        return self.engine.afterstates(boards=boards, out=out, features=features)
 
     def placement_actions(self, slots, out=None):
         """TetrisBatch.placement_actions of the engine, on its stream: the
         uint8 actions step() takes, toward the chosen placement slots."""
         return self.engine.placement_actions(slots, out=out)
 
-    def policy_linear(self, weights, out=None):
+    def policy_linear(self, weights, out=None, features="base", allowed=None):
         """TetrisBatch.policy_linear of the engine, on its stream: every env's
         best placement under linear feature weights (slot, action, score and
-        feature row) in one launch."""
-        return self.engine.policy_linear(weights, out=out)
+        feature row) in one launch.  features='bcts': over the 18 rows;
+        allowed: a slot mask (a Reachable, or int32 [n, S])."""
+        return self.engine.policy_linear(weights, out=out, features=features, allowed=allowed)
 
-    def play_linear(self, weights, k, returns=None, episodes=None, obs="none", placements=False):
+    def play_linear(self, weights, k, returns=None, episodes=None, obs="none", placements=False, features="base"):
         """TetrisBatch.play_linear of the engine: k steps of policy_linear ->
         step in one library call, straight on the engine (no info, no
         final_observation: with autoreset a finished env simply plays on);
         returns the (returns, episodes) accumulators.  placements=True: at
-        placement level (policy_linear -> step_placements)."""
+        placement level (policy_linear -> step_placements).  features='bcts':
+        with the 18 rows."""
         return self.engine.play_linear(weights, k, returns=returns, episodes=episodes, obs=obs,
-                                       placements=placements)
+                                       placements=placements, features=features)
 
     def place(self, slots, out=None):
         """TetrisBatch.place of the engine, on its stream: commit a placement

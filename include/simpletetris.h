@@ -38,7 +38,9 @@ extern "C" {
  * refused by the host package when it binds the symbol); so are
  * st_after_slots / st_afterstates / st_placement_actions,
  * st_policy_linear / st_play_linear, st_place / st_step_placements /
- * st_play_linear_placements and st_reachable / st_route_actions.
+ * st_play_linear_placements, st_reachable / st_route_actions and
+ * st_feature_rows / st_afterstates_set / st_policy_linear_set /
+ * st_play_linear_set.
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -557,6 +559,80 @@ int st_step_placements(st_ctx *ctx, const int32_t *d_slots, uint8_t *d_placed,
 int st_play_linear_placements(st_ctx *ctx, const float *d_weights, int64_t n_w, int64_t k,
                               int64_t *d_return, int32_t *d_episodes,
                               uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
+
+/* Feature sets: the rows Dellacherie's and the BCTS (Thiery & Scherrer)
+ * players are built from, behind the rows of st_after_feat.
+ *
+ * ST_FEATS_BASE is st_after_feat, ST_AFTER_NFEAT = 11 rows.  ST_FEATS_BCTS has
+ * ST_AFTER_NFEAT + ST_AFTER_NEXT = 18 rows: rows 0..10 are st_after_feat's, word
+ * for word; row ST_AFTER_NFEAT + v is st_after_ext's value v.
+ *
+ * B is the slot's afterstate board after _clear_lines and before any death
+ * erase -- exactly the board st_afterstates returns in d_boards -- B[x][y] with
+ * x in 0..W-1 and y = 0 the top row.  The piece's cells are
+ * rotated^rot(shapes[id]) at (x + i, ST_AFTER_Y + j), unclipped.  A HOLE is an
+ * empty cell with a filled cell above it in its column (_count_holes,
+ * tetris_env.py:218-220).  All rows are int32 and 0 on an invalid slot. */
+enum st_feature_set { ST_FEATS_BASE = 0, ST_FEATS_BCTS = 1 };
+enum st_after_ext {            /* extended row index = ST_AFTER_NFEAT + value */
+    ST_AFTER_EXT_LANDING2,   /* 2 * H - 1 - (ymin + ymax), ymin / ymax the smallest / largest row of the
+                                piece's cells (unclipped: ymin may be negative): twice the height of the
+                                piece's middle above the floor, a bottom-row cell spanning heights 0..1.
+                                Dellacherie's landing height is LANDING2 / 2; doubled, the row is an integer */
+    ST_AFTER_EXT_ERODED,     /* LINES * (the piece's cells that _set_piece wrote, i.e. inside the board,
+                                and that lay in a row that was then cleared) */
+    ST_AFTER_EXT_ROW_TRANS,  /* over all H rows of B, a filled wall left of column 0 and right of column
+                                W - 1: the horizontally adjacent pairs that differ.  An empty row counts 2
+                                (an empty 10x20 board: 40); the "occupied rows only" convention is this
+                                row plus a multiple of ROWS and a constant */
+    ST_AFTER_EXT_COL_TRANS,  /* over all W columns, cell (x, H) = the floor filled and nothing above row 0:
+                                the pairs (y, y + 1), y in 0..H-1, that differ (an empty 10x20 board: 10) */
+    ST_AFTER_EXT_WELLS,      /* a well cell is an empty cell whose left and right neighbours are filled
+                                (walls count as filled); the sum over maximal vertical runs of well cells
+                                in a column of d (d + 1) / 2, d the run's length.  Covered well cells
+                                count like open ones */
+    ST_AFTER_EXT_HOLE_DEPTH, /* sum over holes of the number of filled cells above the hole in its column */
+    ST_AFTER_EXT_HOLE_ROWS,  /* the rows of B that hold at least one hole */
+    ST_AFTER_NEXT
+};
+/* The number of rows of a feature set: 11 or 18; ST_EINVAL for any other set. */
+int st_feature_rows(int32_t set);
+/* st_afterstates with the rows of `set`: d_feat int32 [n_envs][rows][S],
+ * rows = st_feature_rows(set); d_boards as for st_afterstates (the boards do
+ * not depend on the set).  With ST_FEATS_BASE it is st_afterstates: the same
+ * kernel, outputs equal bit for bit.  Reads and leaves the state, ordering and
+ * gates as st_afterstates does.  ST_EINVAL for a NULL ctx or d_feat or a bad
+ * set, ST_ESTATE before st_seed + st_reset, both before any GPU call. */
+int st_afterstates_set(st_ctx *ctx, int32_t set, int32_t *d_feat, uint32_t *d_boards, st_stream stream);
+/* st_policy_linear over the rows of `set`, with an optional slot mask.
+ * d_weights: float32 [n_w][rows].  The score is st_policy_linear's chain over
+ * the set's rows in index order, acc = acc + w[r] * (float)feat[r] from 0.0f,
+ * every product and every sum rounded on its own; ties go to the lowest slot.
+ * d_allowed: int32 [n_envs][S] or NULL.  A slot is a CANDIDATE iff it is valid
+ *   and (d_allowed == NULL or d_allowed[e][s] != 0); an invalid slot is never
+ *   one, whatever the mask says.  The layout is st_reachable's d_steps, so a
+ *   player can be confined to the slots the live piece can really reach.
+ * The choice is the candidate with the largest score; no candidate gives slot
+ * -1, action 2, score 0.0f and a zero d_best column.
+ * d_slots / d_actions / d_scores as for st_policy_linear; d_best int32
+ * [rows][n_envs] or NULL.  With ST_FEATS_BASE and a NULL mask it is
+ * st_policy_linear: the same kernel.  State, ordering and gates as there.
+ * ST_EINVAL for a NULL ctx, NULL d_weights, a bad set, n_w < 1 or all four
+ * outputs NULL; ST_ESTATE before st_seed + st_reset; both before any GPU call. */
+int st_policy_linear_set(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w,
+                         const int32_t *d_allowed, int32_t *d_slots, uint8_t *d_actions,
+                         float *d_scores, int32_t *d_best, st_stream stream);
+/* st_play_linear (placements == 0) or st_play_linear_placements (placements
+ * != 0) with the rows of `set`: d_weights float32 [n_w][rows]; the same
+ * loop, the same ring of reward / done rows and the same sums, the same
+ * first-call rule (see st_step_placements), d_return / d_episodes / d_obs /
+ * d_reward / d_done, k <= 0 and both autoreset modes as there.  It takes no
+ * mask: one would be stale after the first step.  ST_EINVAL for a NULL ctx,
+ * NULL d_weights, a bad set or n_w < 1, ST_ESTATE before st_seed + st_reset,
+ * both before any GPU call. */
+int st_play_linear_set(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w, int64_t k,
+                       int32_t placements, int64_t *d_return, int32_t *d_episodes,
+                       uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
 
 /* Synthetic action source used by the benchmark and the parity tests:
  * d_out[e] = splitmix64(seed ^ ((t << 32) ^ (global_offset + e))) % 7. */
