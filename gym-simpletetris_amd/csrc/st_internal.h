@@ -80,6 +80,7 @@ struct KParams {
 hipError_t launch_seed(const KParams &p, hipStream_t s);
 hipError_t launch_reset(const KParams &p, hipStream_t s);
 hipError_t launch_step(const KParams &p, hipStream_t s);
+hipError_t launch_step_packed(const KParams &p, hipStream_t s);  // st_step_packed.hip: k_step<.., F32 = false, ..>
 // st_step_export: p.obs / p.reward / p.done are the step's outputs and the record's sources
 hipError_t launch_step_export(const KParams &p, int64_t env, uint32_t parts, uint32_t *out, hipStream_t s);
 hipError_t launch_rollout(const KParams &p, hipStream_t s);

@@ -17,9 +17,13 @@
 // each side are all-ones walls, so a collision test is four AND-tests with no
 // bounds checks and hard_drop is a count-trailing-zeros per piece column.
 //
-// Five translation units are built from this file: the library's kernels (as
-// it is); with ST_STEP_EXPORT_TU defined (st_step_export.hip), k_step_export
-// and its launcher alone; with ST_AFTERSTATES_TU defined (st_afterstates.hip),
+// Six translation units are built from this file: the library's kernels (as
+// it is); with ST_STEP_PACKED_TU defined (st_step_packed.hip), st_step's
+// packed-obs k_step instantiations (the prologue-draw schedule) and their
+// launcher alone -- in the library's own module they changed the code emitted
+// for the float32 k_step, which keeps the parent schedule and, apart from
+// them, its instruction stream; with ST_STEP_EXPORT_TU defined
+// (st_step_export.hip), k_step_export and its launcher alone; with ST_AFTERSTATES_TU defined (st_afterstates.hip),
 // k_afterstates, k_placement_actions, k_place, k_policy_linear, k_play_sum and
 // their launchers alone; with ST_REACHABLE_TU defined (st_reachable.hip),
 // k_reachable's instantiations and their launchers alone; with
@@ -32,7 +36,8 @@
 // k_rollout2.
 #include "st_internal.h"
 
-#if defined(ST_STEP_EXPORT_TU) || defined(ST_AFTERSTATES_TU) || defined(ST_REACHABLE_TU) || defined(ST_FEATURES_TU)
+#if defined(ST_STEP_EXPORT_TU) || defined(ST_STEP_PACKED_TU) || defined(ST_AFTERSTATES_TU) || defined(ST_REACHABLE_TU) || \
+    defined(ST_FEATURES_TU)
 #define ST_SIDE_TU 1  // not the library's own translation unit
 #endif
 #if defined(ST_AFTERSTATES_TU) || defined(ST_FEATURES_TU)
@@ -166,6 +171,10 @@ constexpr int kRD = kNT;
 // step: K = 2,000 4.67-4.72 -> 4.64-4.67 us, profiles/r03/ab_step_lprio.txt).
 constexpr int kDrawPrio = 2;
 constexpr int kLogicPrio = 1;
+// (packed st_step's draw wave stays at the launch's priority 0 throughout: its
+// prologue draw runs beside a logic wave's action phase and lock path, and at
+// 1 or 2 between B0 and the ballot wait it cost the logic wave more than it
+// gained -- round 16 A/B, profiles/r16/ab_draw_fill_prio.txt)
 // (soff: a wave-uniform part of the offset, the instruction's scalar offset;
 // in range, off + soff lies within the resource; with off = kOff the access
 // is dropped whatever soff is)
@@ -581,8 +590,9 @@ __device__ __forceinline__ uint32_t mt_pack(int idx, int pg, int cur) {
 // word: pv << 21 | ok << 24 | c << 25, c = the MT words its draw
 // consumed (6 bits; a draw of > 62 words has p < 2^-62), so the reference's
 // state -- the one before the preview was drawn -- is c words back
-// (k_mt_sync).  ok = 0 (a host-written or synced state): the next spawn draws
-// its piece first, then the preview.  Bit 31 is zero.  (Round 1 kept a
+// (k_mt_sync).  ok = 0 (a host-written or synced state, and an env whose last
+// lock was st_step's, until the next st_step's prologue draws the preview):
+// a kernel that spawns from it draws its piece first.  Bit 31 is zero.  (Round 1 kept a
 // 4-word draw-window cache per env flagged there; with the 64-word successor
 // chunks the draw wave's window wait is off the critical chain, and the
 // cache's 16 B per env and step bought nothing: removed, A/B +-0.)
@@ -628,8 +638,10 @@ __device__ __forceinline__ u32x4 mt_ld16(const MtRes &rs, bool on, uint32_t word
 struct MtPre {
     uint32_t w[kMtWin];
 };
-// WIN = 8 for st_step (P(8 rejections) <= 2^-8: a dependent load for a few
-// lanes per step, off the critical chain); 16 in rollouts.
+// WIN = 16 in packed st_step's prologue and in the rollouts: P(16
+// rejections) <= 2^-16; 8 in the float32 step, whose draw sits behind the
+// lock, off the logic wave's chain (P(8 rejections) <= 2^-8: a dependent load
+// for a few lanes per step).
 template <int WIN>
 __device__ __forceinline__ void mt_pre_load(const MtRes &rs, uint32_t mtst, bool want, MtPre &q) {
     int idx, pg, cur;
@@ -1077,8 +1089,21 @@ __device__ __forceinline__ uint32_t pack_piece(int id, int rot, int ax, int ay, 
 // (the two-wave st_step hands data between them through it).  Plain words
 // only (no vector-type members: a __shared__ object must be trivially
 // constructible).
+// packed st_step only (an empty base in the rollouts and the float32 step,
+// whose LDS does not change):
+// fb = 1 once the lock ballot (lockm) is written (owner: logic); pkm / pkg:
+// the box descriptor {m, g} of every lane's next piece at rotation 0, under
+// f2 like pick1 (owner: draw), so that the logic wave takes the flag, the
+// pick and its descriptor in ONE LDS round trip
+template <bool ON>
+struct StepOnceLds {
+    uint32_t fb;
+    uint32_t pkm[kWave], pkg[kWave];
+};
+template <>
+struct StepOnceLds<false> {};
 template <int WT, bool F32, int KSTEPS>
-struct StepLds {
+struct StepLds : StepOnceLds<KSTEPS == 1 && !F32> {
     static constexpr int kCols = (WT ? WT : kMaxW) + 2 * kPad;
     // board columns L[x + kPad][lane], all-ones walls at both ends
     uint32_t L[kCols * kWave] __attribute__((aligned(16)));
@@ -1105,17 +1130,19 @@ struct StepLds {
     uint32_t f1, f2;  // = t + 1 once step t's draw mask / first picks are written
 };
 
-// The two waves of a step kernel (step_logic and step_draw, below).  st_step
-// runs TWO waves per 64 envs: the logic wave
+// The two waves of a step kernel (step_logic and step_draw_once / step_draw,
+// below).  st_step runs TWO waves per 64 envs: the logic wave
 // (action, lock path, board / obs / counter outputs) and the draw wave (MT
 // words, the next-generation block, the piece draw), so the draw no longer
 // sits on the logic wave's chain.  That works because spawns take a piece
-// drawn one spawn AHEAD (the "preview", kept in the MT state word): a spawn
-// needs no draw result from the same step, and the draw wave's draw -- the
-// next preview -- is only stored.  The reference's RNG sequence is unchanged
-// (every spawn / reset still consumes the next draw, with the shape counts of
-// that moment: the preview is drawn right after the previous spawn's count
-// update, and counts change only at spawns); st_mt_sync rewinds the preview's
+// drawn AHEAD of the spawn (the "preview", kept in the MT state word): a
+// spawn needs no draw result from the same step.  The rollouts draw the next
+// preview right behind the lock that consumed the last one; st_step leaves it
+// missing at the lock and draws it in the next launch's prologue, before that
+// launch's lock ballot (step_draw_once).  The reference's RNG sequence is
+// unchanged either way (every spawn / reset still consumes the next draw,
+// with the shape counts of that moment: counts change only at spawns, so any
+// time between two spawns is that moment); st_mt_sync rewinds a preview's
 // words for the host.  k_rollout2 (KSTEPS == 0) runs the same two waves.
 
 __device__ __forceinline__ void wg_barrier() {
@@ -1177,6 +1204,26 @@ __device__ __forceinline__ void lds_flag_wait(uint32_t *f, uint32_t v) {
     while (__hip_atomic_load((lds_u32 *)f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != v)
         __builtin_amdgcn_s_sleep(1);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+// Wait for flag f == v and take three words it guards in the same LDS round
+// trip: the flag is read first, the data right behind it, and the flag is
+// checked after all have returned (see above: relaxed LDS atomics, written
+// with lds_st before lds_flag_set; a wave's LDS operations execute in order;
+// the signal fence between the flag read and the data reads keeps the
+// compiler from moving a data read ahead of it).  Wave-uniform.
+[[maybe_unused]] __device__ __forceinline__ void lds_flag_wait_take3(uint32_t *f, uint32_t v, const uint32_t *a, const uint32_t *b,
+                                                    const uint32_t *c, uint32_t &va, uint32_t &vb, uint32_t &vc) {
+    for (;;) {
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        const uint32_t fv = __hip_atomic_load((lds_u32 *)f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        va = lds_ld(a);
+        vb = lds_ld(b);
+        vc = lds_ld(c);
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        if (__builtin_amdgcn_readfirstlane(fv) == v) break;
+        __builtin_amdgcn_s_sleep(1);
+    }
 }
 // A progress counter read as a relaxed LDS atomic (no wait by itself).
 __device__ __forceinline__ uint32_t lds_flag_get(uint32_t *f) {
@@ -1486,27 +1533,33 @@ __device__ __forceinline__ void dump_stamps(const KParams &p, int lane, int K, u
 //  - B0 (wg_barrier) once, after each wave has staged its share of the state
 //    -- logic: the board, its counter groups, the zeroed overlay plane; draw:
 //    its counter groups, the walls, the piece table, the F4 table;
-//  - VEC: after B0 both take the gate's early return, before B1 and before any
-//    global store of either wave;
-//  - B1 (wg_barrier) once per step in both: before it the logic wave
-//    publishes the lock ballot in lockm[t & 1] (owner: logic; the draw wave
-//    reads it after B1);
+//  - VEC: after B0 both take the gate's early return, before the ballot and
+//    before any global store of either wave;
+//  - the lock ballot, lockm[t & 1] (owner: logic).  Rollouts and the float32
+//    step (step_draw): B1 (wg_barrier) once per step in both waves, the
+//    ballot written before it and read after it.  Packed st_step
+//    (step_draw_once; ONCE in step_logic): no barrier -- the ballot goes out under the
+//    one-way flag fb = 1 and the logic wave goes on; the draw wave, which has
+//    drawn by then, waits for fb and reads it;
 //  - logic -> draw: drawm (the lanes whose lock consumed the preview) under
 //    the flag f1 = t + 1, written and waited for only without same-step
 //    auto-reset (with it every locking lane draws);
 //  - draw -> logic: pick1 (the first draw of a lane without a valid preview)
-//    under the flag f2 = t + 1, set every step, waited for only where a lane
-//    needs it (rare);
+//    under the flag f2 = t + 1, set every step, waited for only where a
+//    spawning lane had no preview (st_step: every lock right behind a lock);
+//  - no wait cycle: each wave sets the flag it owns before it waits on one of
+//    the other's -- the draw wave f2 before it waits for fb (and f1), the
+//    logic wave fb (and f1) before its f2 waits (overlay paint, spawn id);
 //  - rollouts: mtw[t & 1] (owner: draw) is the MT word after step t, which
 //    the logic wave's step t + 1 reads after its B1;
-//  - each wave zeroes the flag it owns (logic f1, draw f2) before B0.
+//  - each wave zeroes the flags it owns (logic f1 and fb, draw f2) before B0.
 // LATE COUNTERS (LCL), st_step (not st_step_vec, whose info snapshot needs
 // every counter of every env).  The prologue's load burst carries only what
 // every env needs at the step start -- board, action, time, piece word,
 // MT word -- and the lock-only counter rows are read per locking lane
 // once the lock decision is known (logic: score .. deaths, issued before
-// B1, needed at the end of the lock path; draw: the shape counts, issued
-// with the MT window after B1)
+// the ballot, needed at the end of the lock path; the draw wave stages the
+// shape counts and the MT word in the prologue)
 // (round 4, profiles/r04/ab_late_counters.txt: K = 2,000 4.642-4.643 ->
 // 4.605-4.635 us; reading the draw wave's shape counts late as well was
 // +6% -- its post-B1 chain, window + counts + draw parameters, became the
@@ -1546,6 +1599,7 @@ __device__ __forceinline__ void step_logic(const KParams &p, StepLds<WT, F32, KS
     // lines -- the counter rows' HBM reads gone, timing only)
     const uint32_t *ssrc = reinterpret_cast<const uint32_t *>(p.stats) + ((kAblate & 1024u) ? 0 : e0);
     constexpr bool OVP = KSTEPS == 1;
+    constexpr bool ONCE = KSTEPS == 1 && !F32;  // the prologue-draw schedule (step_draw_once)
     constexpr bool LCL = KSTEPS == 1 && !VEC;  // late counters, see above
     BoardRows<WT> br;
     br.load(p.board + e0, wc, W);
@@ -1575,7 +1629,10 @@ __device__ __forceinline__ void step_logic(const KParams &p, StepLds<WT, F32, KS
             if ((WT || 4 * q < W) && 4 * q + lrow < W)
                 *reinterpret_cast<uint4 *>(&sm.OV[(4 * q + lrow + kPad) * kWave + lcc]) = make_uint4(0u, 0u, 0u, 0u);
     }
-    if (lane == 0) sm.f1 = 0u;
+    if (lane == 0) {
+        sm.f1 = 0u;
+        if constexpr (ONCE) sm.fb = 0u;
+    }
     wg_barrier();  // B0: the staged state is complete
     if (gate_shut<VEC>(p, gate_v)) return;
     // an action outside value_action_map in any step of this launch (the
@@ -1607,6 +1664,7 @@ __device__ __forceinline__ void step_logic(const KParams &p, StepLds<WT, F32, KS
     // st_step's obs overlay of a spawn: its preview's descriptor, read in the
     // action phase's LDS round trip (not on the store phase's chain)
     [[maybe_unused]] uint2 pd_pv = make_uint2(0u, 0u);
+    [[maybe_unused]] uint32_t pick_rd = 0;  // st_step: the draw wave's pick, read with the flag at the overlay paint
     {
         // ---- action + drop, gravity + lock delay (move_cand, move_resolve) ----
         // Current and candidate descriptors and their columns are read in one
@@ -1641,9 +1699,12 @@ __device__ __forceinline__ void step_logic(const KParams &p, StepLds<WT, F32, KS
         if (lane == 0) {
             sm.lockm[t & 1][0] = (uint32_t)m;
             sm.lockm[t & 1][1] = (uint32_t)(m >> 32);
+            // st_step: the ballot goes out under a one-way flag -- the draw
+            // wave, which draws before it reads the ballot, is not waited for
+            if constexpr (ONCE) lds_flag_set(&sm.fb, 1u);
         }
     }
-    wg_barrier();  // B1: the draw wave learns which lanes lock
+    if constexpr (!ONCE) wg_barrier();  // B1 (rollouts, the float32 step): the draw wave learns which lanes lock
     if constexpr (KSTEPS != 1) ST_STAMP(10);
     if constexpr (KSTEPS != 1) {
         if (t > 0) mt0 = sm.mtw[(t - 1) & 1][lane];
@@ -1772,9 +1833,23 @@ __device__ __forceinline__ void step_logic(const KParams &p, StepLds<WT, F32, KS
             // (the preview's descriptor was read with the action's)
             uint2 pd = pd_pv;
             const bool need1 = draw && !pv_ok(mt0);
-            if (__ballot(need1)) {
-                lds_flag_wait(&sm.f2, (uint32_t)t + 1u);
-                if (need1) pd = wc.tab((int)sm.pick1[lane] * 4);
+            if constexpr (!ONCE) {
+                if (__ballot(need1)) {  // (the float32 step)
+                    lds_flag_wait(&sm.f2, (uint32_t)t + 1u);
+                    if (need1) pd = wc.tab((int)sm.pick1[lane] * 4);
+                }
+            } else if (__ballot(need1)) {
+                // (common: every wave with a lane that locks right behind a
+                // lock) the same wait as above, with the pick and its
+                // descriptor taken in the flag's LDS round trip; the draw
+                // wave has set f2 before, as a rule
+                [[maybe_unused]] uint64_t w0 = 0;
+                if constexpr (STAMP) w0 = __builtin_amdgcn_s_memtime();
+                uint32_t pm, pg;
+                lds_flag_wait_take3(&sm.f2, (uint32_t)t + 1u, &sm.pkm[lane], &sm.pkg[lane], &sm.pick1[lane], pm, pg,
+                                    pick_rd);
+                if constexpr (STAMP) tstamp[9] = __builtin_amdgcn_s_memtime() - w0;  // (word 9: cycles spent on f2)
+                if (need1) pd = make_uint2(pm, pg);
             }
             const uint32_t om = spawn ? pd.x : desc.x, og = spawn ? pd.y : desc.y;
             const int ox = spawn ? W / 2 : ax, oy = spawn ? 0 : ay;
@@ -1878,7 +1953,9 @@ __device__ __forceinline__ void step_logic(const KParams &p, StepLds<WT, F32, KS
     int sid = pv_id(mt0);
     {
         const bool need1 = draw && !pv_ok(mt0);
-        if (__ballot(need1)) {
+        if constexpr (ONCE) {
+            if (need1) sid = (int)pick_rd;  // (taken with the flag at the overlay paint)
+        } else if (__ballot(need1)) {
             lds_flag_wait(&sm.f2, (uint32_t)t + 1u);
             if (need1) sid = (int)sm.pick1[lane];
         }
@@ -2132,6 +2209,172 @@ __device__ __forceinline__ void step_logic(const KParams &p, StepLds<WT, F32, KS
 }
 
 // The draw wave: MT words, the next-generation block, the piece draw.
+// Packed st_step's draw wave (KSTEPS == 1, !F32; the float32 step keeps
+// step_draw, see there): the draw runs in the PROLOGUE, not behind
+// the lock ballot.  A lock draws nothing: it spawns the preview and leaves the
+// MT word with the preview missing (pv_ok == 0, the state st_seed / st_mt_sync
+// / a host write leave too).  The next st_step's draw wave fills it: the MT
+// word row is its first load, lanes without a preview fetch their 16-word
+// window inside the prologue's burst, and between B0 and the ballot -- while
+// the logic wave runs its action phase, and this wave used to idle at B1 --
+// they draw with the staged counts (the counts of the moment: counts change
+// only at spawns, so this is the draw the reference's next _new_piece makes).
+// The picks go out in pick1 (their descriptors in pkm / pkg) under f2 = 1, set unconditionally and before
+// this wave waits for the ballot flag fb (each wave sets the flag it owns
+// before it waits on the other's: no wait cycle).  After the ballot:
+//  - drew, no lock: the MT word with the new, valid preview;
+//  - drew, locks: the logic wave spawns the pick (pick1); the advanced index
+//    with the preview missing again, and the pick's count;
+//  - valid preview, locks: index unchanged, preview missing, its count;
+//  - everything else: nothing (but the chunk lane's progress).
+// A death without auto-reset (locks, not in drawm) keeps or gains its valid
+// preview: the next st_reset spawns it.
+// Stamps: 0 start, 1 B0 passed, 9 window arrived, 3 draws done (f2 set),
+// 10 ballot seen, 4 chunk stored, 11 commit issued (2 and 8 unused: tools/stamps.py
+// tells the layouts apart by them).
+template <int WT, int HT, bool F32, bool STAMP, bool SC0, bool VEC>
+__device__ __forceinline__ void step_draw_once(const KParams &p, StepLds<WT, F32, 1> &sm) {
+    constexpr int KSTEPS = 1;  // (ST_STAMP)
+    [[maybe_unused]] uint64_t tstamp[12] = {};
+    [[maybe_unused]] uint32_t tacc[12] = {};
+    [[maybe_unused]] uint64_t tlast = 0;
+    [[maybe_unused]] uint64_t draw_kind = 0;  // stamp build: 1 = a lane twisted, 2 = a draw ran past its window
+    const uint32_t kAblate = ablate_bits(p);
+    [[maybe_unused]] uint64_t rt0 = 0;
+    if constexpr (STAMP) {
+        rt0 = __builtin_amdgcn_s_memrealtime();
+        tlast = __builtin_amdgcn_s_memtime();
+    }
+    ST_STAMP(0);
+    const WaveCtx wc(p, sm);
+    const int lane = wc.lane;
+    const int64_t e0 = wc.e0, e = wc.e, sd = wc.sd;
+    const bool real = wc.real;
+
+    // ---- loads: the MT word per lane first (the windows hang on it), then
+    // the staged rows (the shape counts and the MT word; VEC: groups 2-3) ----
+    const auto rs = buf_rsrc(p.stats, (uint32_t)kHotRows * (uint32_t)sd * 4u);
+    const uint32_t eo = (uint32_t)e * 4u;
+    const uint32_t mt0 = __builtin_amdgcn_raw_buffer_load_b32(rs, real ? eo : kOff,
+                                                              (uint32_t)ST_STAT_MT_INDEX * (uint32_t)sd * 4u, 0);
+    const uint32_t *ssrc = reinterpret_cast<const uint32_t *>(p.stats) + ((kAblate & 1024u) ? 0 : e0);
+    constexpr bool LCL = !VEC;  // late counters, see above
+    // (the staged rows carry the MT word once more, 16 B per lane with the
+    // shape counts: the logic wave reads its preview bits from LDS after B0,
+    // and the per-lane load above exists only so that the windows' addresses
+    // do not wait for a 16-B row load and its LDS transposition)
+    StagedRows<LCL, true> sq;
+    sq.load(wc, ssrc, kAblate);
+    const uint32_t gate_v = gate_load<VEC>(p);
+    build_tables<WT, F32>(p, sm, lane);
+    // the windows of the lanes without a preview, inside the prologue's burst
+    // (ablation 2: no draws; 524288: the words read as zeros -- timing only)
+    const MtRes mrs = mt_res(p.mt + e0 * kMtPitch, lane);
+    const bool fill = real && !pv_ok(mt0) && !(kAblate & 2u);
+    // 16 words (the rollouts' window): the logic wave of a lane that locks
+    // right behind a lock takes this draw's pick in the same launch, so a
+    // draw that runs past its window -- a dependent load -- holds its logic
+    // wave up (8 words: ~3 waves per step, which then ended the launch last)
+    constexpr int kWin = 16;
+    MtPre pre;
+    mt_pre_load<kWin>(mrs, mt0, fill && !(kAblate & 524288u), pre);
+    sq.store(wc);
+    if (lane == 0) sm.f2 = 0u;
+    wg_barrier();  // B0: the staged state is complete
+    if (gate_shut<VEC>(p, gate_v)) return;
+    if constexpr (STAMP) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    ST_STAMP(1);
+    // this step's next-generation chunk: operands issued behind the windows
+    MtChunk chunk;
+    mt_chunk_issue(mrs, mt0, real && !(kAblate & (2u | 1048576u)), lane, chunk);  // (1048576: no chunks, timing only)
+    // the counts of the moment (_choose_shape's, tetris_env.py:183-191)
+    int32_t cnt[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) cnt[i] = (int32_t)wc.ss(ST_STAT_COUNT0 + i);
+    const DrawPar dpar = draw_par(cnt);
+    if constexpr (STAMP) {  // diagnostic split of the draw: MT-word wait | compute
+        mt_win_consume<kWin>(pre);
+        ST_STAMP(9);
+    }
+    uint32_t mtst = mt0;  // packed (mt_pack + preview bits)
+    const int pk = draw_core<kWin>(fill, dpar, mtst, p.mt + e0 * kMtPitch, sm.S, lane, pre, fill);
+    // the piece the env's next spawn takes: the preview, old or just drawn,
+    // with its descriptor at the spawn rotation
+    const int sid = fill ? pk : pv_id(mt0);
+    {
+        const uint2 pd = wc.tab(sid * 4);
+        lds_st(&sm.pkm[lane], pd.x);
+        lds_st(&sm.pkg[lane], pd.y);
+        lds_st(&sm.pick1[lane], (uint32_t)sid);
+    }
+    if (lane == 0) lds_flag_set(&sm.f2, 1u);
+    ST_STAMP(3);
+    if constexpr (STAMP) {  // 1: a draw started a generation, 2: a draw ran past its window
+        const int i0 = (int)(mt0 & 0x3FFu), i1 = (int)(mtst & 0x3FFu);
+        draw_kind = (__ballot(fill && i1 < i0) ? 1u : 0u) | (__ballot(fill && i1 >= i0 && i1 - i0 > kWin) ? 2u : 0u);
+    }
+    const uint32_t mt_drawn = pv_pack(mtst, pk, mt_consumed(mt0, mtst));
+    int32_t csid = cnt[0];  // the spawned shape's count after a spawn (_new_piece :199)
+#pragma unroll
+    for (int i = 1; i < 7; ++i) csid = sid == i ? cnt[i] : csid;
+    csid += 1;
+
+    // ---- the ballot: which lanes lock (and, without same-step auto-reset,
+    // which of those consume the preview) ----
+    lds_flag_wait(&sm.fb, 1u);
+    ST_STAMP(10);
+    const uint32_t lw = lane < 32 ? sm.lockm[0][0] : sm.lockm[0][1];
+    bool dr = (lw >> (lane & 31)) & 1u;
+    // this step's next-generation chunk (its operands arrived long ago);
+    // its env's progress advances unless that env's own draw switched
+    // generations (finishing the successor itself: same words)
+    const int chunk_pg = mt_chunk_store<kST>(mrs, lane, chunk);
+    const bool chunk_me = lane == chunk.l;
+    ST_STAMP(4);
+    if (p.autoreset != ST_AUTORESET_SAME_STEP) {
+        lds_flag_wait(&sm.f1, 1u);
+        const uint32_t w = lane < 32 ? sm.drawm[0] : sm.drawm[1];
+        dr = (w >> (lane & 31)) & 1u;
+    }
+    // a spawn leaves the preview missing (at the index after this step's draw, if any)
+    uint32_t mt_out = dr ? (mtst & kMtLow) : (fill ? mt_drawn : mt0);
+    if (chunk_me && (mt_out & (1u << 20)) == (mt0 & (1u << 20))) {
+        int i2, pg2, c2;
+        mt_unpack(mt_out, i2, pg2, c2);
+        mt_out = mt_keep(mt_out, mt_pack(i2, chunk_pg, c2));
+    }
+    // this wave's changed counter rows straight from the registers, one
+    // coalesced dword per lane and row: the MT word, and the count of the
+    // spawned shape
+    // (ablation 2048: the lock-path counter stores dropped, timing only)
+    const bool cst = !(kAblate & (2048u | 32768u));
+    const bool mst = cst && !(kAblate & 131072u) && (dr || fill || chunk_me);
+    const bool kst = cst && !(kAblate & 65536u) && dr;
+    __builtin_amdgcn_raw_buffer_store_b32(mt_out, rs, mst ? eo + (uint32_t)ST_STAT_MT_INDEX * (uint32_t)sd * 4u : kOff, 0,
+                                          kST);
+    __builtin_amdgcn_raw_buffer_store_b32((uint32_t)csid, rs,
+                                          kst ? eo + (uint32_t)(ST_STAT_COUNT0 + sid) * (uint32_t)sd * 4u : kOff, 0, kST);
+    if constexpr (VEC) {  // st_step_vec's info snapshot: the shape counts after the step
+        const auto ri = buf_rsrc(p.info, (uint32_t)ST_NSTAT * (uint32_t)p.n * 4u);
+#pragma unroll
+        for (int i = 0; i < 7; ++i)
+            __builtin_amdgcn_raw_buffer_store_b32(
+                (uint32_t)(cnt[i] + (dr && i == sid)), ri,
+                real ? ((uint32_t)(ST_STAT_COUNT0 + i) * (uint32_t)p.n + (uint32_t)e) * 4u : kOff, 0, kNT);
+    }
+    ST_STAMP(11);
+    wave_sync();
+    dump_stamps<STAMP, 1, true>(p, lane, 1, tstamp, tacc, tlast, rt0, draw_kind);
+}
+
+// The draw wave on the schedule with the draw BEHIND the lock ballot: B1
+// every step, then the window, the draw of the next preview (lanes without a
+// valid preview -- every env whose last lock was a packed st_step's -- draw
+// their piece first) and the commit.  k_rollout2 (KSTEPS == 0) runs it, and so
+// do st_step's float32 instantiations (KSTEPS == 1, F32): their launch is
+// write-bound on the float32 obs, and with the prologue draw they measured
+// 11.84-12.03 us per step against 11.44-11.46 (profiles/r16/ab_step_prologue_draw.txt),
+// so they keep this schedule, instruction for instruction.
 template <int WT, int HT, bool F32, bool STAMP, int KSTEPS, bool SC0, bool VEC = false>
 __device__ __forceinline__ void step_draw(const KParams &p, StepLds<WT, F32, KSTEPS> &sm) {
     static_assert(!VEC || KSTEPS == 1, "VEC: st_step only");
@@ -2225,7 +2468,7 @@ __device__ __forceinline__ void step_draw(const KParams &p, StepLds<WT, F32, KST
         if (!(kAblate & 2u)) {
             mt_win_consume<kWin>(pre);
             const bool need1 = dr_spec && !pv_ok(mt0);
-            if (__ballot(need1)) {  // rare: after st_seed / st_mt_sync / a host-written state
+            if (__ballot(need1)) {  // after a packed st_step's lock, st_seed, st_mt_sync or a host-written state
                 // the piece first, with the counts before the spawn
                 int32_t c0[7];
 #pragma unroll
@@ -2334,7 +2577,8 @@ __global__ __launch_bounds__(2 * kWave) void k_step(uint32_t *board, int32_t *st
     p.n = n;
     __shared__ StepLds<WT, F32, 1> sm;
     if (threadIdx.x < kWave) step_logic<WT, HT, F32, STAMP, 1, SC0, VEC>(p, sm);
-    else step_draw<WT, HT, F32, STAMP, 1, SC0, VEC>(p, sm);
+    else if constexpr (F32) step_draw<WT, HT, F32, STAMP, 1, SC0, VEC>(p, sm);
+    else step_draw_once<WT, HT, F32, STAMP, SC0, VEC>(p, sm);
 }
 
 // ---------------------------------------------------------------- rollout
@@ -3391,8 +3635,8 @@ __global__ __launch_bounds__(256) void k_export(KParams p, int64_t env, const ui
 // st_step_export: k_step (packed outputs, no stamps, not gated) with the
 // export record of one env written by the workgroup that stepped it -- the
 // single-env surface's step and read-back in ONE launch.  Both waves run
-// step_logic / step_draw unchanged and meet at one more workgroup barrier
-// (each has passed B0 and B1 once: neither role returns early without VEC);
+// step_logic / step_draw_once unchanged and meet at one more workgroup barrier
+// (each has passed B0 once: neither role returns early without VEC);
 // behind it the workgroup's 128 threads write the record from what the two
 // waves stored to global memory moments before: obs / reward / done and the
 // hot counter rows (logic wave), the count rows, the MT index word, the MT
@@ -3428,7 +3672,7 @@ __global__ __launch_bounds__(2 * kWave) void k_step_export(uint32_t *board, int3
     p.done = done;
     __shared__ StepLds<WT, false, 1> sm;
     if (threadIdx.x < kWave) step_logic<WT, HT, false, false, 1, SC0, false>(p, sm);
-    else step_draw<WT, HT, false, false, 1, SC0, false>(p, sm);
+    else step_draw_once<WT, HT, false, false, SC0, false>(p, sm);
     if ((int64_t)blockIdx.x != env / kWave) return;
     __builtin_amdgcn_s_setprio(0);  // the tail is nobody's critical chain
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have reached L2
@@ -4862,6 +5106,30 @@ hipError_t launch_route_actions(const KParams &p, const int32_t *slots, uint8_t 
                        steps, actions);
     return hipGetLastError();
 }
+#elif defined(ST_STEP_PACKED_TU)
+// st_step's packed-obs launches (every k_step<.., F32 = false, ..>: the
+// prologue-draw schedule, step_draw_once); launch_step keeps the float32 ones
+hipError_t launch_step_packed(const KParams &p, hipStream_t s) {
+    const dim3 grid((unsigned)(p.stride / kWave)), block(2 * kWave);  // logic + draw wave
+    const bool sc0 = !(p.flags & kScoringFlags);
+    if (p.final_obs || p.info || p.gate) {  // st_step_vec: the vector env's outputs (VEC); gated launches
+        if (p.W == 10 && p.H == 20) {
+            if (sc0) hipLaunchKernelGGL((k_step<10, 20, false, false, true, true>), grid, block, 0, s, ST_STEP_ARGS(p));
+            else hipLaunchKernelGGL((k_step<10, 20, false, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
+        } else {
+            hipLaunchKernelGGL((k_step<0, 0, false, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
+        }
+    } else if (p.stamps && p.W == 10 && p.H == 20) {
+        if (sc0) hipLaunchKernelGGL((k_step<10, 20, false, true, true>), grid, block, 0, s, ST_STEP_ARGS(p));
+        else hipLaunchKernelGGL((k_step<10, 20, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
+    } else if (p.W == 10 && p.H == 20) {
+        if (sc0) hipLaunchKernelGGL((k_step<10, 20, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
+        else hipLaunchKernelGGL((k_step<10, 20, false>), grid, block, 0, s, ST_STEP_ARGS(p));
+    } else {
+        hipLaunchKernelGGL((k_step<0, 0, false>), grid, block, 0, s, ST_STEP_ARGS(p));
+    }
+    return hipGetLastError();
+}
 #else  // the library's own translation unit
 
 hipError_t launch_seed(const KParams &p, hipStream_t s) {
@@ -4876,31 +5144,24 @@ hipError_t launch_reset(const KParams &p, hipStream_t s) {
 }
 
 hipError_t launch_step(const KParams &p, hipStream_t s) {
+    // packed obs: the prologue-draw kernels, a module of their own (st_step_packed.hip)
+    if (p.obs_f32 == nullptr) return launch_step_packed(p, s);
     const dim3 grid((unsigned)(p.stride / kWave)), block(2 * kWave);  // logic + draw wave
-    const bool f32 = p.obs_f32 != nullptr;
     const bool sc0 = !(p.flags & kScoringFlags);
     if (p.final_obs || p.info || p.gate) {  // st_step_vec: the vector env's outputs (VEC); gated launches
         if (p.W == 10 && p.H == 20) {
-            if (f32 && sc0) hipLaunchKernelGGL((k_step<10, 20, true, false, true, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-            else if (f32) hipLaunchKernelGGL((k_step<10, 20, true, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-            else if (sc0) hipLaunchKernelGGL((k_step<10, 20, false, false, true, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-            else hipLaunchKernelGGL((k_step<10, 20, false, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
+            if (sc0) hipLaunchKernelGGL((k_step<10, 20, true, false, true, true>), grid, block, 0, s, ST_STEP_ARGS(p));
+            else hipLaunchKernelGGL((k_step<10, 20, true, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
         } else {
-            if (f32) hipLaunchKernelGGL((k_step<0, 0, true, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-            else hipLaunchKernelGGL((k_step<0, 0, false, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
+            hipLaunchKernelGGL((k_step<0, 0, true, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
         }
     } else if (p.stamps && p.W == 10 && p.H == 20) {
-        if (f32) hipLaunchKernelGGL((k_step<10, 20, true, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-        else if (sc0) hipLaunchKernelGGL((k_step<10, 20, false, true, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-        else hipLaunchKernelGGL((k_step<10, 20, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
+        hipLaunchKernelGGL((k_step<10, 20, true, true>), grid, block, 0, s, ST_STEP_ARGS(p));
     } else if (p.W == 10 && p.H == 20) {
-        if (f32 && sc0) hipLaunchKernelGGL((k_step<10, 20, true, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-        else if (f32) hipLaunchKernelGGL((k_step<10, 20, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-        else if (sc0) hipLaunchKernelGGL((k_step<10, 20, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-        else hipLaunchKernelGGL((k_step<10, 20, false>), grid, block, 0, s, ST_STEP_ARGS(p));
+        if (sc0) hipLaunchKernelGGL((k_step<10, 20, true, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
+        else hipLaunchKernelGGL((k_step<10, 20, true>), grid, block, 0, s, ST_STEP_ARGS(p));
     } else {
-        if (f32) hipLaunchKernelGGL((k_step<0, 0, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-        else hipLaunchKernelGGL((k_step<0, 0, false>), grid, block, 0, s, ST_STEP_ARGS(p));
+        hipLaunchKernelGGL((k_step<0, 0, true>), grid, block, 0, s, ST_STEP_ARGS(p));
     }
     return hipGetLastError();
 }

@@ -290,8 +290,10 @@ int st_copy(void *dst, const void *src, int64_t bytes, st_stream stream);
 
 /* The step kernels keep each env's MT19937 generation double-buffered (the
  * next generation is computed a few words per draw into a second buffer and
- * becomes current at index 624) and draw every env's next piece one spawn
- * ahead (the "preview", whose words the reference has not consumed yet), so
+ * becomes current at index 624) and draw every env's next piece ahead of its
+ * spawn (the "preview", whose words the reference has not consumed yet: the
+ * rollouts draw it right behind a lock, st_step at the start of the step
+ * after one, so an env may also hold none between launches), so
  * between steps ST_STAT_MT_INDEX carries engine bits above bit 9 and the
  * current words may sit in the second buffer.  st_mt_sync (on `stream`)
  * brings every env back to CPython's form -- words [0, 624) of its mt row and

@@ -27,11 +27,25 @@ dnames = ["loads+B0", "until L's action", "B1", "MT words wait", "draws", "commi
 acc, dacc = [], []
 
 
+# prologue-draw layout (round 16): the draw wave draws before the lock ballot --
+# stamps 0 1 9 3 10 4 11 6 7, stamps 2 and 8 unused (0); the logic wave's word 9
+# is the cycles it waited for f2 at the overlay paint (0: no lane needed a pick)
+dnames16 = ["loads+B0", "MT words wait", "draws", "ballot wait", "chunk", "commit", "state stores issue", "store drain"]
+f2w = []
+prologue_draw = False
+
+
 def record():
-    global names
+    global names, dnames, prologue_draw
     b._L.st_debug_stamps(b._ctx, ctypes.c_void_p(buf.ctypes.data), buf.size)
     full = buf.reshape(nw, W).astype(np.int64)
-    if (full[:, 9] != 0).all():  # round 6's early stores: logic stamp 9 after them, before the lock path
+    prologue_draw = bool((full[:, 16 + 2] == 0).all())
+    if prologue_draw:
+        names = ["loads+B0", "action+drop", "ballot+lock path", "reward/done issue", "paint+f2 wait+LDS reads",
+                 "obs+board stores", "spawn-id f2 wait", "obs+counters", "state stores issue", "store drain"]
+        acc.append(np.diff(full[:, [0, 1, 2, 3, 14, 15, 8, 4, 5, 6, 7]], axis=1))
+        f2w.append(full[:, 9].copy())
+    elif (full[:, 9] != 0).all():  # round 6's early stores: logic stamp 9 after them, before the lock path
         names = ["loads+B0", "action+drop", "B1+early stores", "lock path", "late stores", "spawn-id wait",
                  "obs+counters", "state stores issue", "store drain"]
         acc.append(np.diff(full[:, [0, 1, 2, 9, 3, 8, 4, 5, 6, 7]], axis=1))
@@ -41,7 +55,11 @@ def record():
         acc.append(np.diff(full[:, [0, 1, 2, 3, 14, 15, 8, 4, 5, 6, 7]], axis=1))
     else:
         acc.append(np.diff(full[:, [0, 1, 2, 3, 8, 4, 5, 6, 7]], axis=1))
-    dacc.append(np.diff(full[:, [16 + i for i in (0, 1, 2, 10, 9, 4, 11, 6, 7)]], axis=1))
+    if prologue_draw:
+        dnames = dnames16
+        dacc.append(np.diff(full[:, [16 + i for i in (0, 1, 9, 3, 10, 4, 11, 6, 7)]], axis=1))
+    else:
+        dacc.append(np.diff(full[:, [16 + i for i in (0, 1, 2, 10, 9, 4, 11, 6, 7)]], axis=1))
     r = full[:, 10:15].copy()
     r[:, 4] = full[:, 30]  # draw kind (written by the draw wave)
     rts.append(np.concatenate([r, full[:, 28:30]], axis=1))
@@ -98,6 +116,19 @@ d0 = r[:, :, 5] - r[:, :, 0].min(axis=1, keepdims=True)
 d1 = r[:, :, 6] - r[:, :, 0].min(axis=1, keepdims=True)
 print(f"draw wave: start median {np.median(d0)*ns:.0f} ns, end median {np.median(d1)*ns:.0f} p90 {np.percentile(d1, 90)*ns:.0f} "
       f"max {d1.max(1).mean()*ns:.0f}; ends after its logic wave in {np.mean(d1 > t1)*100:.0f}% of workgroups")
+# which role owns the launch's last wave end (the launch ends with it), per step
+le, de = t1.max(1), d1.max(1)
+print(f"per-step end maxima ns: logic mean {le.mean()*ns:.0f} median {np.median(le)*ns:.0f}; "
+      f"draw mean {de.mean()*ns:.0f} median {np.median(de)*ns:.0f}")
+print(f"last wave of the launch ({len(le)} steps, 10 ns ticks): a draw wave in {np.mean(de > le)*100:.1f}% of steps, "
+      f"a logic wave in {np.mean(le > de)*100:.1f}%, tie {np.mean(le == de)*100:.1f}%; "
+      f"draw end max - logic end max: median {np.median(de - le)*ns:.0f} ns, p90 {np.percentile(de - le, 90)*ns:.0f} ns")
+if prologue_draw:
+    w = np.concatenate(f2w)
+    bw = da[:, 3]
+    print(f"logic wave f2 wait at the overlay paint, cycles: median {np.median(w):.0f} p90 {np.percentile(w, 90):.0f} "
+          f"max {w.max()}; waves that waited at all {np.mean(w > 0)*100:.0f}%; of those median {np.median(w[w > 0]) if (w > 0).any() else 0:.0f}")
+    print(f"draw wave ballot wait, cycles: median {np.median(bw):.0f} p90 {np.percentile(bw, 90):.0f} max {bw.max()}")
 xcc = r[0, :, 3] & 0xF
 hw = r[0, :, 2]
 cu = (hw >> 8) & 0xF
@@ -124,10 +155,10 @@ top = np.sort(tot_w, axis=1)[:, -k:]
 print(f"the {k} slowest waves per step: mean total {top.mean():.0f} cycles")
 
 kind = r[:, :, 4]  # 1: a lane twisted its MT state, 2: a draw ran past the 8 prefetched words
-for kd, nm in ((0, "plain"), (1, "twist"), (2, "past 8 words"), (3, "both")):
+for kd, nm in ((0, "plain"), (1, "twist"), (2, "past its window"), (3, "both")):  # window: 8 words, 16 since round 16
     m = kind == kd
     if m.any():
         dl = da.reshape(len(dacc), nw, -1)
-        print(f"draw kind {nm:13s}: {m.sum() / len(acc):6.1f} waves/step, draw-wave draws median "
-              f"{np.median(dl[:, :, 4][m]):6.0f}, logic total median {np.median(tot_w[m]):6.0f} cycles")
+        print(f"draw kind {nm:15s}: {m.sum() / len(acc):6.1f} waves/step, draw-wave draws median "
+              f"{np.median(dl[:, :, 2 if prologue_draw else 4][m]):6.0f}, logic total median {np.median(tot_w[m]):6.0f} cycles")
 print("kind of the slowest wave per step:", np.bincount(kind[np.arange(len(acc)), slow], minlength=4).tolist())
