@@ -3,6 +3,7 @@
 // method it replaces there.  Owns the device state; launches the kernels of
 // st_kernels.hip on the caller's stream.
 #include <algorithm>
+#include <cmath>
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -630,12 +631,19 @@ int st_policy_linear(st_ctx *c, const float *d_weights, int64_t n_w, int32_t *d_
 // on it) and st_play_linear_placements (commit true: the policy commits its
 // slot, then the step on the constant hard drop)
 // set: the rows the policy scores (st_play_linear_set; the base set runs the two older kernels)
+// look: st_play_lookahead -- the policy is the two-ply kernel (d_weights its second-ply rows, look->weights1 its
+// first-ply rows or null), committing its own choice
+struct PlayLookahead {
+    const float *weights1;
+    float dead_value;
+};
 static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weights, int64_t n_w, int64_t k,
                      int64_t *d_return, int32_t *d_episodes, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
-                     st_stream stream, int32_t set = ST_FEATS_BASE) {
+                     st_stream stream, int32_t set = ST_FEATS_BASE, const PlayLookahead *look = nullptr) {
     if (!c || !d_weights) return fail(ST_EINVAL, "%s: null argument", fn);
     if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS) return fail(ST_EINVAL, "%s: unknown feature set %d", fn, set);
     if (n_w < 1) return fail(ST_EINVAL, "%s: n_w %lld < 1", fn, (long long)n_w);
+    if (look && !std::isfinite(look->dead_value)) return fail(ST_EINVAL, "%s: dead_value is not finite", fn);
     if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "%s before st_seed + st_reset", fn);
     if (k <= 0) return ST_OK;
     DeviceGuard g(c->device);
@@ -653,7 +661,10 @@ static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weig
     int row = 0;
     for (int64_t i = 0; i < k; ++i) {
         const bool last = i == k - 1;
-        if (set != ST_FEATS_BASE)
+        if (look)
+            ST_HIP(st::launch_policy_lookahead(params(c), set, true, look->weights1, d_weights, n_w, look->dead_value,
+                                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s));
+        else if (set != ST_FEATS_BASE)
             ST_HIP(st::launch_policy_linear_set(params(c), set, commit, d_weights, n_w, nullptr, nullptr,
                                                 commit ? nullptr : q.act, nullptr, nullptr, s));
         else if (commit) ST_HIP(st::launch_policy_linear_commit(params(c), d_weights, n_w, s));
@@ -729,6 +740,43 @@ int st_play_linear_set(st_ctx *c, int32_t set, const float *d_weights, int64_t n
                        st_stream stream) {
     return play_impl(c, "st_play_linear_set", placements != 0, d_weights, n_w, k, d_return, d_episodes, d_obs,
                      d_reward, d_done, stream, set);
+}
+
+int st_next_piece(st_ctx *c, uint8_t *d_next, st_stream stream) {
+    if (!c || !d_next) return fail(ST_EINVAL, "st_next_piece: null argument");
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_next_piece before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_next_piece: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_next_piece(params(c), d_next, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_policy_lookahead(st_ctx *c, int32_t set, const float *d_weights1, const float *d_weights2, int64_t n_w,
+                        float dead_value, const int32_t *d_allowed, int32_t *d_slots, int32_t *d_slots2,
+                        uint8_t *d_actions, float *d_scores, float *d_scores_all, int32_t *d_slots2_all,
+                        st_stream stream) {
+    if (!c || !d_weights2) return fail(ST_EINVAL, "st_policy_lookahead: null argument");
+    if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS)
+        return fail(ST_EINVAL, "st_policy_lookahead: unknown feature set %d", set);
+    if (n_w < 1) return fail(ST_EINVAL, "st_policy_lookahead: n_w %lld < 1", (long long)n_w);
+    if (!d_slots && !d_slots2 && !d_actions && !d_scores && !d_scores_all && !d_slots2_all)
+        return fail(ST_EINVAL, "st_policy_lookahead: every output is null");
+    if (!std::isfinite(dead_value)) return fail(ST_EINVAL, "st_policy_lookahead: dead_value is not finite");
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_policy_lookahead before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_policy_lookahead: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_policy_lookahead(params(c), set, false, d_weights1, d_weights2, n_w, dead_value, d_allowed,
+                                       d_slots, d_slots2, d_actions, d_scores, d_scores_all, d_slots2_all,
+                                       (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_play_lookahead(st_ctx *c, int32_t set, const float *d_weights1, const float *d_weights2, int64_t n_w,
+                      float dead_value, int64_t k, int64_t *d_return, int32_t *d_episodes, uint32_t *d_obs,
+                      int32_t *d_reward, uint8_t *d_done, st_stream stream) {
+    const PlayLookahead look{d_weights1, dead_value};
+    return play_impl(c, "st_play_lookahead", true, d_weights2, n_w, k, d_return, d_episodes, d_obs, d_reward, d_done,
+                     stream, set, &look);
 }
 
 int st_place(st_ctx *c, const int32_t *d_slots, uint8_t *d_placed, st_stream stream) {

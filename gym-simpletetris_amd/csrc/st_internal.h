@@ -110,6 +110,16 @@ hipError_t launch_afterstates_set(const KParams &p, int set, int32_t *feat, uint
 hipError_t launch_policy_linear_set(const KParams &p, int set, bool commit, const float *weights, int64_t n_w,
                                     const int32_t *allowed, int32_t *slots, uint8_t *actions, float *scores,
                                     int32_t *best, hipStream_t s);
+// st_next_piece: next uint8 [n] or null (then only the missing previews are drawn)
+hipError_t launch_next_piece(const KParams &p, uint8_t *next, hipStream_t s);
+// st_policy_lookahead / st_play_lookahead (commit: the chosen first-ply slot is committed like launch_place):
+// launch_next_piece, then the two-ply kernel over the rows of `set` -- weights1 float [n_w][rows] or null, weights2
+// float [n_w][rows], allowed int32 [n][S] or null; slots / slots2 int32 [n], actions uint8 [n], scores float [n],
+// scores_all float [n][S], slots2_all int32 [n][S], any null
+hipError_t launch_policy_lookahead(const KParams &p, int set, bool commit, const float *weights1,
+                                   const float *weights2, int64_t n_w, float dead_value, const int32_t *allowed,
+                                   int32_t *slots, int32_t *slots2, uint8_t *actions, float *scores,
+                                   float *scores_all, int32_t *slots2_all, hipStream_t s);
 // st_play_linear: adds rows 0 .. rows - 1 of reward int32 [rows][n] / done uint8 [rows][n] to acc_return
 // int64 [n] / acc_episodes int32 [n] (either null) and copies the last row to out_reward / out_done (either null)
 hipError_t launch_play_sum(const KParams &p, const int32_t *reward, const uint8_t *done, int rows, int64_t *acc_return,

@@ -124,6 +124,11 @@ SIG = {
     "st_afterstates_set": ([_vp, _i32, _vp, _vp, _vp], ctypes.c_int),
     "st_policy_linear_set": ([_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_play_linear_set": ([_vp, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_next_piece": ([_vp, _vp, _vp], ctypes.c_int),
+    "st_policy_lookahead": ([_vp, _i32, _vp, _vp, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+                            ctypes.c_int),
+    "st_play_lookahead": ([_vp, _i32, _vp, _vp, _i64, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+                          ctypes.c_int),
     "st_debug_stamps": ([_vp, _vp, _i64], ctypes.c_int),
     "st_last_error": ([], ctypes.c_char_p),
     "st_abi_version": ([], ctypes.c_int),
@@ -158,7 +163,7 @@ def load(path: str = LIB_PATH):
             if ab_override:
                 continue
             # an addition that did not change the ABI number (st_step_export, st_afterstates,
-            # st_policy_linear, st_place, st_reachable, st_afterstates_set):
+            # st_policy_linear, st_place, st_reachable, st_afterstates_set, st_next_piece):
             # the library on disk was built before it
             raise ImportError(f"{path}: no symbol {name} (a stale build of ABI {abi}: rebuild it with "
                               "`make -C gym-simpletetris_amd/csrc`)")

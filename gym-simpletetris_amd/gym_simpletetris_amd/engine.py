@@ -277,6 +277,31 @@ class LinearChoice:
         return feat[row]
 
 
+class LookaheadChoice:
+    """TetrisBatch.policy_lookahead()'s result: `slots` int32 [n] (the chosen
+    first-ply slot, -1: no candidate), `slots2` int32 [n] (the best second-ply
+    slot behind it, -1: none), `actions` uint8 [n] (as step() takes them) and
+    `scores` float32 [n]; with table=True also `scores_all` float32 [n, S] and
+    `slots2_all` int32 [n, S], the score and best second-ply slot of every
+    candidate (0.0 / -1 elsewhere), else None.  A field not asked for (`out`) is
+    None."""
+
+    def __init__(self, slots, slots2, actions, scores, scores_all=None, slots2_all=None):
+        self.slots, self.slots2, self.actions, self.scores = slots, slots2, actions, scores
+        self.scores_all, self.slots2_all = scores_all, slots2_all
+
+
+def _dead_value(dead_value) -> float:
+    """policy_lookahead's / play_lookahead's dead_value as a finite float."""
+    if isinstance(dead_value, bool) or not isinstance(dead_value, (int, float, np.integer, np.floating)):
+        raise TypeError(f"dead_value must be a real number, got {type(dead_value)}")
+    with np.errstate(over="ignore"):
+        v = float(np.float32(dead_value))
+    if not np.isfinite(v):
+        raise ValueError(f"dead_value must be finite in float32, got {dead_value!r}")
+    return v
+
+
 class TetrisBatch:
     """Batched engine.  `autoreset`: 'none' (exact reference semantics; the
     caller resets done envs, like `if done: env.reset()`) or 'same_step'
@@ -1066,6 +1091,111 @@ class TetrisBatch:
         else:
             C.check(self._L.st_play_linear_set(self._ctx, fset, _ptr(w), w.shape[0], int(k), int(bool(placements)),
                                                *tail))
+        return returns, episodes
+
+    # ------------------------------------------------------------ next piece, two-ply player
+    def next_piece(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The piece every env's next spawn takes (st_next_piece): uint8 [n],
+        the id in SHAPE_NAMES order of the shape _choose_shape()
+        (tetris_env.py:183-191) would return for the env now -- the piece
+        behind the next lock, or behind a reset.  Changes nothing the
+        reference can see: board, piece, counters and the MT19937 state as
+        sync_mt() / save() give it stay the same, and so does every later
+        step.  `out`: a uint8 [n] device tensor to write."""
+        if out is None:
+            out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
+        else:
+            _check_tensor(out, "out", (self.n,), (torch.uint8,), self.device)
+        C.check(self._L.st_next_piece(self._ctx, _ptr(out), self._stream()))
+        return out
+
+    def _lookahead_weights(self, weights, first_weights, features):
+        w2 = self._weights(weights, features)
+        w1 = None
+        if first_weights is not None:
+            w1 = self._weights(first_weights, features)
+            if w1.shape != w2.shape:
+                raise ValueError(f"first_weights: shape {tuple(w1.shape)} is not weights' {tuple(w2.shape)}")
+        return w1, w2
+
+    def policy_lookahead(self, weights, first_weights=None, dead_value: float = -1.0e6, features: str = "base",
+                         allowed=None, table: bool = False, out=None) -> LookaheadChoice:
+        """policy_linear with the next piece known, in one launch
+        (st_policy_lookahead).  Every candidate slot s1 of the current piece
+        (valid, and allowed where `allowed` is given: policy_linear's mask) that
+        does not end the game is followed by every placement s2 of
+        next_piece() on its afterstate board, with the counters the lock of s1
+        leaves; score(s1) = S1 + T in float32, S1 the chain score of s1's rows
+        under `first_weights` (0 if None), T the largest chain score over the
+        valid s2 under `weights` (ties to the lowest s2), or `dead_value` where
+        s1 is dead or leaves no valid s2.  The candidate with the largest score
+        wins, ties to the lowest slot.  weights / first_weights: as
+        policy_linear takes them, both of one shape; row e % n_w is env e's.
+        Returns a LookaheadChoice: .slots (-1: no candidate, then slots2 -1,
+        action 2, score 0), .slots2, .actions, .scores, and with table=True
+        .scores_all float32 [n, S] / .slots2_all int32 [n, S] for every
+        candidate (0 / -1 elsewhere).  Changes nothing the reference can see
+        (next_piece's rule).  `out`: a (slots, slots2, actions, scores) tuple
+        -- with table=True (slots, slots2, actions, scores, scores_all,
+        slots2_all) -- of device tensors to write; None entries are not
+        computed (at least one must be given)."""
+        n, S = self.n, self.n_slots
+        fset = _feature_set(features)[0]
+        w1, w2 = self._lookahead_weights(weights, first_weights, features)
+        dv = _dead_value(dead_value)
+        if isinstance(allowed, Reachable):
+            allowed = allowed.steps
+        if allowed is not None:
+            _check_tensor(allowed, "allowed", (n, S), (torch.int32,), self.device)
+        names = ("slots", "slots2", "actions", "scores", "scores_all", "slots2_all")[: 6 if table else 4]
+        shapes = ((n,), (n,), (n,), (n,), (n, S), (n, S))
+        dtypes = (torch.int32, torch.int32, torch.uint8, torch.float32, torch.float32, torch.int32)
+        if out is None:
+            out = tuple(torch.empty(sh, dtype=dt, device=self.device) for _, sh, dt in zip(names, shapes, dtypes))
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != len(names):
+                raise ValueError(f"out: a ({', '.join(names)}) tuple, None for an output not wanted")
+            if all(t is None for t in out):
+                raise ValueError("out: at least one output tensor is needed")
+            for t, name, sh, dt in zip(out, names, shapes, dtypes):
+                if t is not None:
+                    _check_tensor(t, "out " + name, sh, (dt,), self.device)
+        out = tuple(out) + (None,) * (6 - len(out))
+        C.check(self._L.st_policy_lookahead(self._ctx, fset, _ptr(w1), _ptr(w2), w2.shape[0], dv, _ptr(allowed),
+                                            *(_ptr(t) for t in out), self._stream()))
+        return LookaheadChoice(*out)
+
+    def play_lookahead(self, weights, k: int, first_weights=None, dead_value: float = -1.0e6,
+                       features: str = "base", returns: Optional[torch.Tensor] = None,
+                       episodes: Optional[torch.Tensor] = None, obs: str = "packed", out=None):
+        """k pieces of policy_lookahead(weights, first_weights, dead_value) ->
+        step_placements(its slots), enqueued by ONE library call
+        (st_play_lookahead), identical to the k rounds by hand: placement-level
+        play_linear with the two-ply choice.  `returns` / `episodes`, both
+        autoreset modes, k = 0 and the one-stream rule are play_linear's;
+        returns (returns, episodes).  The last step's outputs are in .reward,
+        .done and (obs='packed') .obs, or in `out`, an (obs, reward, done)
+        triple as step() takes it."""
+        if obs not in ("packed", "none"):
+            raise ValueError("obs must be 'packed' or 'none'")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+            raise ValueError(f"k must be an integer >= 0, got {k!r}")
+        fset = _feature_set(features)[0]
+        w1, w2 = self._lookahead_weights(weights, first_weights, features)
+        dv = _dead_value(dead_value)
+        if returns is None:
+            returns = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        else:
+            _check_tensor(returns, "returns", (self.n,), (torch.int64,), self.device)
+        if episodes is None:
+            episodes = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        else:
+            _check_tensor(episodes, "episodes", (self.n,), (torch.int32,), self.device)
+        o_t, r_t, d_t = (self.obs, self.reward, self.done) if out is None \
+            else _check_out(out, self.width, self.n, self.device)
+        C.check(self._L.st_play_lookahead(self._ctx, fset, _ptr(w1), _ptr(w2), w2.shape[0], dv, int(k),
+                                          _ptr(returns), _ptr(episodes), _ptr(o_t) if obs == "packed" else None,
+                                          _ptr(r_t), _ptr(d_t), self._stream()))
         return returns, episodes
 
 

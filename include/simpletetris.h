@@ -40,7 +40,8 @@ extern "C" {
  * st_policy_linear / st_play_linear, st_place / st_step_placements /
  * st_play_linear_placements, st_reachable / st_route_actions and
  * st_feature_rows / st_afterstates_set / st_policy_linear_set /
- * st_play_linear_set.
+ * st_play_linear_set, and st_next_piece / st_policy_lookahead /
+ * st_play_lookahead.
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -635,6 +636,80 @@ int st_policy_linear_set(st_ctx *ctx, int32_t set, const float *d_weights, int64
 int st_play_linear_set(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w, int64_t k,
                        int32_t placements, int64_t *d_return, int32_t *d_episodes,
                        uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
+
+/* Next piece.  d_next[e] (uint8 [n_envs]) is the id, in shape_names order
+ * (tetris_env.py:19), of the shape _choose_shape() (tetris_env.py:183-191)
+ * would return for env e in its present state.  _choose_shape reads
+ * shape_counts and the env's MT19937 state and nothing else; shape_counts
+ * changes only at a spawn (_new_piece, :193-200) and clear() (:306-315) keeps
+ * it, so this is the piece the env's next _new_piece takes, whether that spawn
+ * follows a lock or a reset (the reference itself has no preview attribute: it
+ * draws only when it spawns).
+ * The call changes nothing the reference can see: board, piece and counters
+ * stay bit for bit the same, so does the MT19937 state in the form st_mt_sync /
+ * st_save / st_export_env give it, and every later step gives the results it
+ * would have given without the call.  (Engine-private: an env that holds no
+ * drawn piece for its next spawn draws it here and keeps it, as st_step does
+ * at its start.)  A host-written CPython state (index 0..624) is a valid input,
+ * a draw that runs across index 624 included.
+ * Not gated, consumes no gate, needs no st_mt_sync before or after; ordered by
+ * `stream` like every other call.  ST_EINVAL for a NULL ctx or d_next,
+ * ST_ESTATE before st_seed + st_reset, both before any GPU call. */
+int st_next_piece(st_ctx *ctx, uint8_t *d_next, st_stream stream);
+
+/* Two-ply player: st_policy_linear_set with the next piece known.
+ * First ply: the slots s1, their validity and their rows f1 are
+ *   st_afterstates_set(set)'s for the env's current piece, word for word;
+ *   R = st_feature_rows(set).  s1 is a CANDIDATE iff it is valid and
+ *   (d_allowed == NULL or d_allowed[e][s1] != 0): st_policy_linear_set's rule
+ *   and its int32 [n_envs][S] layout.
+ * Second ply: for a candidate s1 with f1[ST_AFTER_DEAD] = 0 let X(s1) be the
+ *   state the placement step of s1 leaves (st_step_placements; in the
+ *   reference: the piece set to the slot's rotation at (x, 0), then
+ *   step(hard_drop), tetris_env.py:243-304): its board is the slot's afterstate
+ *   board, its live piece is st_next_piece's, its holes / piece_height counters
+ *   are as :283-297 leave them.  f2(s1, s2) and the validity of s2 are what
+ *   st_afterstates_set(set) returns in state X(s1), word for word,
+ *   ST_AFTER_REWARD included.  The mask does not apply to s2.
+ * Scores, float32, every product and every sum rounded on its own:
+ *   S1(s1) = st_policy_linear_set's chain over f1 with row e % n_w of
+ *     d_weights1 (float [n_w][R]); 0.0f if d_weights1 is NULL.
+ *   M2(s1) = the largest chain score over the valid s2 with row e % n_w of
+ *     d_weights2 (float [n_w][R], required); ties go to the lowest s2.
+ *   score(s1) = S1(s1) + T(s1), one float32 add; T = M2(s1) where a valid s2
+ *     exists; T = dead_value where s1 is dead or no s2 is valid, and the slot's
+ *     second-ply slot is then -1.
+ * Choice: the candidate with the largest score, ties to the lowest s1.  No
+ *   candidate: slot -1, second slot -1, action 2, score 0.0f.  Weights and
+ *   dead_value must be finite; otherwise the result is unspecified, except
+ *   that slots stay in [-1, S) and nothing faults.
+ * Outputs, each may be NULL but not all six: d_slots int32 [n_envs]; d_slots2
+ *   int32 [n_envs], the best s2 behind the chosen s1; d_actions uint8
+ *   [n_envs], st_placement_actions's rule for the chosen s1; d_scores float
+ *   [n_envs]; d_scores_all float [n_envs][S] and d_slots2_all int32
+ *   [n_envs][S]: score(s1) and its best s2 for every candidate, 0.0f / -1 for
+ *   every other slot.
+ * State, ordering and gates as for st_next_piece: nothing the reference can see
+ * changes.  ST_EINVAL for a NULL ctx, NULL d_weights2, a bad set, n_w < 1, all
+ * six outputs NULL or a non-finite dead_value; ST_ESTATE before st_seed +
+ * st_reset; both before any GPU call. */
+int st_policy_lookahead(st_ctx *ctx, int32_t set, const float *d_weights1, const float *d_weights2,
+                        int64_t n_w, float dead_value, const int32_t *d_allowed, int32_t *d_slots,
+                        int32_t *d_slots2, uint8_t *d_actions, float *d_scores, float *d_scores_all,
+                        int32_t *d_slots2_all, st_stream stream);
+/* st_play_linear_placements with st_policy_lookahead's choice: k times
+ * (st_policy_lookahead, d_allowed NULL, its chosen s1 committed by the same
+ * launch -> the step on the constant hard drop), identical to k rounds of
+ * st_policy_lookahead + st_step_placements(d_slots) by hand.  The ring of
+ * reward / done rows and the sums, the first-call rule (see
+ * st_step_placements), the one-buffer-per-context ordering rule, both
+ * autoreset modes, k <= 0 and the last step's d_obs / d_reward / d_done are
+ * st_play_linear_placements's.  It takes no mask (st_play_linear_set's reason).
+ * ST_EINVAL for a NULL ctx, NULL d_weights2, a bad set, n_w < 1 or a non-finite
+ * dead_value, ST_ESTATE before st_seed + st_reset, both before any GPU call. */
+int st_play_lookahead(st_ctx *ctx, int32_t set, const float *d_weights1, const float *d_weights2,
+                      int64_t n_w, float dead_value, int64_t k, int64_t *d_return, int32_t *d_episodes,
+                      uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
 
 /* Synthetic action source used by the benchmark and the parity tests:
  * d_out[e] = splitmix64(seed ^ ((t << 32) ^ (global_offset + e))) % 7. */
