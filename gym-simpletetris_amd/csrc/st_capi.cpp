@@ -40,7 +40,9 @@ struct st_ctx {
     // st_play_linear / st_step_placements / st_play_linear_placements: one
     // allocation made on first use (play_parts) -- a ring of reward rows int32
     // [R][n], the policy's actions uint8 [n], a ring of done rows uint8 [R][n],
-    // the constant action 2 (hard drop) uint8 [n], filled then
+    // the constant action 2 (hard drop) uint8 [n], filled then; behind them
+    // (8-byte aligned) st_play_routed's plans: route uint64 [ST_ROUTE_WORDS][n],
+    // slot, steps and rem int32 [n]
     int32_t *play_buf;
 };
 
@@ -125,6 +127,10 @@ struct PlayParts {
     uint8_t *act;        // uint8 [n]
     uint8_t *ring_done;  // uint8 [R][n]
     uint8_t *twos;       // uint8 [n], every byte 2
+    uint64_t *plan_route;  // st_play_routed: uint64 [ST_ROUTE_WORDS][n]
+    int32_t *plan_slot;    // int32 [n]
+    int32_t *plan_steps;   // int32 [n]
+    int32_t *plan_rem;     // int32 [n]: actions left of the env's plan
 };
 
 int play_parts(st_ctx *c, const char *fn, hipStream_t s, PlayParts *out) {
@@ -132,9 +138,11 @@ int play_parts(st_ctx *c, const char *fn, hipStream_t s, PlayParts *out) {
     const int64_t R = std::max<int64_t>(1, std::min<int64_t>(32, (int64_t(4) << 20) / n));
     PlayParts q;
     q.R = R;
+    const size_t plan_off = ((size_t)n * (size_t)(R * (sizeof(int32_t) + 1) + 2) + 7) & ~(size_t)7;
     if (!c->play_buf) {
         int32_t *buf = nullptr;
-        hipError_t e = hipMalloc(&buf, (size_t)n * (size_t)(R * (sizeof(int32_t) + 1) + 2));
+        const size_t plan_bytes = (size_t)n * (ST_ROUTE_WORDS * sizeof(uint64_t) + 3 * sizeof(int32_t));
+        hipError_t e = hipMalloc(&buf, plan_off + plan_bytes);
         if (e != hipSuccess) return fail(ST_ENOMEM, "%s: hipMalloc failed: %s", fn, hipGetErrorString(e));
         uint8_t *twos = reinterpret_cast<uint8_t *>(buf + R * n) + n + R * n;
         e = hipMemsetAsync(twos, 2, (size_t)n, s);
@@ -149,6 +157,10 @@ int play_parts(st_ctx *c, const char *fn, hipStream_t s, PlayParts *out) {
     q.act = reinterpret_cast<uint8_t *>(q.ring_rew + R * n);
     q.ring_done = q.act + n;
     q.twos = q.ring_done + R * n;
+    q.plan_route = reinterpret_cast<uint64_t *>(reinterpret_cast<uint8_t *>(c->play_buf) + plan_off);
+    q.plan_slot = reinterpret_cast<int32_t *>(q.plan_route + ST_ROUTE_WORDS * n);
+    q.plan_steps = q.plan_slot + n;
+    q.plan_rem = q.plan_steps + n;
     *out = q;
     return ST_OK;
 }
@@ -637,13 +649,20 @@ struct PlayLookahead {
     const float *weights1;
     float dead_value;
 };
+// routed: st_play_routed -- the planner for the envs whose plan has run out, then the pop of every env's next action
+struct PlayRouted {
+    int32_t *pieces;
+};
 static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weights, int64_t n_w, int64_t k,
                      int64_t *d_return, int32_t *d_episodes, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
-                     st_stream stream, int32_t set = ST_FEATS_BASE, const PlayLookahead *look = nullptr) {
+                     st_stream stream, int32_t set = ST_FEATS_BASE, const PlayLookahead *look = nullptr,
+                     const PlayRouted *routed = nullptr) {
     if (!c || !d_weights) return fail(ST_EINVAL, "%s: null argument", fn);
     if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS) return fail(ST_EINVAL, "%s: unknown feature set %d", fn, set);
     if (n_w < 1) return fail(ST_EINVAL, "%s: n_w %lld < 1", fn, (long long)n_w);
     if (look && !std::isfinite(look->dead_value)) return fail(ST_EINVAL, "%s: dead_value is not finite", fn);
+    if (routed && c->cfg.lock_delay > ST_REACH_MAX_LOCK)
+        return fail(ST_EINVAL, "%s: lock_delay %d > %d", fn, c->cfg.lock_delay, ST_REACH_MAX_LOCK);
     if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "%s before st_seed + st_reset", fn);
     if (k <= 0) return ST_OK;
     DeviceGuard g(c->device);
@@ -659,9 +678,14 @@ static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weig
     // Without, the steps write d_reward / d_done themselves.  d_obs is the
     // last step's alone.
     int row = 0;
+    if (routed) ST_HIP(hipMemsetAsync(q.plan_rem, 0, (size_t)n * sizeof(int32_t), s));  // plans are local to a call
     for (int64_t i = 0; i < k; ++i) {
         const bool last = i == k - 1;
-        if (look)
+        if (routed) {
+            ST_HIP(st::launch_routes(params(c), set, d_weights, n_w, nullptr, nullptr, q.plan_rem, q.plan_slot,
+                                     q.plan_route, q.plan_steps, nullptr, s));
+            ST_HIP(st::launch_route_pop(params(c), q.plan_route, q.plan_steps, q.plan_rem, q.act, routed->pieces, s));
+        } else if (look)
             ST_HIP(st::launch_policy_lookahead(params(c), set, true, look->weights1, d_weights, n_w, look->dead_value,
                                                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s));
         else if (set != ST_FEATS_BASE)
@@ -777,6 +801,47 @@ int st_play_lookahead(st_ctx *c, int32_t set, const float *d_weights1, const flo
     const PlayLookahead look{d_weights1, dead_value};
     return play_impl(c, "st_play_lookahead", true, d_weights2, n_w, k, d_return, d_episodes, d_obs, d_reward, d_done,
                      stream, set, &look);
+}
+
+// what st_routes / st_policy_routed check before any GPU call
+static int routes_check(st_ctx *c, const char *fn, bool ptrs_ok) {
+    if (!c || !ptrs_ok) return fail(ST_EINVAL, "%s: null argument", fn);
+    if (c->cfg.lock_delay > ST_REACH_MAX_LOCK)
+        return fail(ST_EINVAL, "%s: lock_delay %d > %d", fn, c->cfg.lock_delay, ST_REACH_MAX_LOCK);
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "%s before st_seed + st_reset", fn);
+    return ST_OK;
+}
+
+int st_routes(st_ctx *c, const int32_t *d_slots, const uint8_t *d_need, uint64_t *d_route, int32_t *d_steps,
+              st_stream stream) {
+    if (const int rc = routes_check(c, "st_routes", d_slots && d_route)) return rc;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_routes: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_routes(params(c), -1, nullptr, 0, d_slots, d_need, nullptr, nullptr, d_route, d_steps, nullptr,
+                             (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_policy_routed(st_ctx *c, int32_t set, const float *d_weights, int64_t n_w, const uint8_t *d_need,
+                     int32_t *d_slots, uint64_t *d_route, int32_t *d_steps, float *d_scores, st_stream stream) {
+    if (!c || !d_weights || !d_slots || !d_route) return fail(ST_EINVAL, "st_policy_routed: null argument");
+    if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS)
+        return fail(ST_EINVAL, "st_policy_routed: unknown feature set %d", set);
+    if (n_w < 1) return fail(ST_EINVAL, "st_policy_routed: n_w %lld < 1", (long long)n_w);
+    if (const int rc = routes_check(c, "st_policy_routed", true)) return rc;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_policy_routed: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_routes(params(c), set, d_weights, n_w, nullptr, d_need, nullptr, d_slots, d_route, d_steps,
+                             d_scores, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_play_routed(st_ctx *c, int32_t set, const float *d_weights, int64_t n_w, int64_t k, int64_t *d_return,
+                   int32_t *d_episodes, int32_t *d_pieces, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
+                   st_stream stream) {
+    const PlayRouted routed{d_pieces};
+    return play_impl(c, "st_play_routed", false, d_weights, n_w, k, d_return, d_episodes, d_obs, d_reward, d_done,
+                     stream, set, nullptr, &routed);
 }
 
 int st_place(st_ctx *c, const int32_t *d_slots, uint8_t *d_placed, st_stream stream) {

@@ -129,6 +129,18 @@ hipError_t launch_reachable(const KParams &p, int32_t *steps, uint8_t *first, hi
 // st_route_actions: slots int32 [n], actions uint8 [n]; steps int32 [n] or null
 hipError_t launch_route_actions(const KParams &p, const int32_t *slots, uint8_t *actions, int32_t *steps,
                                 hipStream_t s);
+// st_routes (set -1: the route to slots_in int32 [n]) / st_policy_routed / st_play_routed (set a feature set: the
+// planner -- weights float [n_w][rows], the chosen slot to slots int32 [n], its score to scores float [n] or null).
+// route uint64 [ST_ROUTE_WORDS][n]; steps int32 [n] or null.  An env is needed iff rem[e] == 0 (rem int32 [n], then
+// set to min(steps, ST_ROUTE_MAX)), or without rem iff need[e] != 0 (need uint8 [n] or null: every env); nothing is
+// written for the others
+hipError_t launch_routes(const KParams &p, int set, const float *weights, int64_t n_w, const int32_t *slots_in,
+                         const uint8_t *need, int32_t *rem, int32_t *slots, uint64_t *route, int32_t *steps,
+                         float *scores, hipStream_t s);
+// st_play_routed: act uint8 [n] = the next action of each env's route (2 where rem[e] == 0), rem falls by one,
+// pieces int32 [n] or null += 1 with a route's last action
+hipError_t launch_route_pop(const KParams &p, const uint64_t *route, const int32_t *steps, int32_t *rem, uint8_t *act,
+                            int32_t *pieces, hipStream_t s);
 hipError_t launch_grayscale(const KParams &p, const uint32_t *obs, int size, int channels,
                             int as_u8, void *out, hipStream_t s);
 hipError_t launch_unwire(int W, int H, int64_t n_global, int shards, int64_t n_cap, const uint32_t *wire,

@@ -206,6 +206,63 @@ class Reachable:
         return self.steps > 0
 
 
+def route_pack(actions) -> np.ndarray:
+    """One route's actions (a sequence of 0..6, at most ROUTE_MAX of them) as
+    its ROUTE_WORDS uint64 words: action i at bits 3 * (i % 21) .. + 2 of word
+    i // 21, every field behind the last one 7, bit 63 clear."""
+    acts = [int(a) for a in actions]
+    if len(acts) > C.ROUTE_MAX or any(a < 0 or a > 6 for a in acts):
+        raise ValueError(f"a route is at most {C.ROUTE_MAX} actions in 0..6")
+    words = [(1 << 63) - 1] * C.ROUTE_WORDS
+    for i, a in enumerate(acts):
+        words[i // 21] ^= (7 - a) << (3 * (i % 21))
+    return np.array(words, np.uint64)
+
+
+def route_unpack(words) -> list:
+    """route_pack's inverse: the actions of one route (its ROUTE_WORDS words,
+    uint64 or the int64 a Routes holds) up to the first field that holds 7."""
+    acts = []
+    for w in np.asarray(words).astype(np.uint64).tolist():
+        for j in range(21):
+            a = (w >> (3 * j)) & 7
+            if a == 7:
+                return acts
+            acts.append(a)
+    return acts
+
+
+class Routes:
+    """TetrisBatch.routes()'s result: `route` int64 [ROUTE_WORDS, n] -- the
+    library's uint64 words, whose bit 63 is 0 -- and `steps` int32 [n], the
+    route's true length (0: the slot cannot be served, every field is 7).
+    action(i): the i-th action of every env, uint8 [n] (7 past a route's end);
+    `length`: the actions the words hold, min(steps, ROUTE_MAX)."""
+
+    def __init__(self, route: torch.Tensor, steps: torch.Tensor):
+        self.route, self.steps = route, steps
+
+    def action(self, i: int) -> torch.Tensor:
+        if not 0 <= i < C.ROUTE_MAX:
+            raise IndexError(f"a route holds actions 0..{C.ROUTE_MAX - 1}")
+        return ((self.route[i // 21] >> (3 * (i % 21))) & 7).to(torch.uint8)
+
+    @property
+    def length(self) -> torch.Tensor:
+        return self.steps.clamp(max=C.ROUTE_MAX)
+
+
+class RoutedChoice:
+    """TetrisBatch.policy_routed()'s result: `slots` int32 [n] (-1: no
+    reachable candidate), `routes` (a Routes) and `scores` float32 [n]."""
+
+    def __init__(self, slots, routes, scores):
+        self.slots, self.routes, self.scores = slots, routes, scores
+
+    def __iter__(self):
+        return iter((self.slots, self.routes, self.scores))
+
+
 # st_policy_greedy's score as linear feature weights: 80 * lines - 12 * holes
 # - 3 * height - 2000 * above (rows by their names in _lib.AFTER)
 GREEDY_WEIGHTS = MappingProxyType(dict(lines=80.0, holes=-12.0, height=-3.0, above=-2000.0))
@@ -930,6 +987,99 @@ class TetrisBatch:
             _check_tensor(steps, "steps", (self.n,), (torch.int32,), self.device)
         C.check(self._L.st_route_actions(self._ctx, _ptr(s), _ptr(out), _ptr(steps), self._stream()))
         return out
+
+    # ------------------------------------------------------------ routes
+    def _need(self, need):
+        if need is None:
+            return None
+        if isinstance(need, torch.Tensor) and need.dtype == torch.bool:
+            need = need.to(torch.uint8)
+        elif not isinstance(need, torch.Tensor):
+            need = torch.as_tensor(np.asarray(need).astype(bool).astype(np.uint8), device=self.device)
+        _check_tensor(need, "need", (self.n,), (torch.uint8,), self.device)
+        return need
+
+    def _routes_out(self, out):
+        if out is None:
+            return (torch.empty((C.ROUTE_WORDS, self.n), dtype=torch.int64, device=self.device),
+                    torch.empty(self.n, dtype=torch.int32, device=self.device))
+        route, steps = out
+        _check_tensor(route, "out route", (C.ROUTE_WORDS, self.n), (torch.int64,), self.device)
+        _check_tensor(steps, "out steps", (self.n,), (torch.int32,), self.device)
+        return route, steps
+
+    def routes(self, slots, need=None, out=None) -> Routes:
+        """The whole shortest way of each env's live piece into its placement
+        slot (st_routes): the actions route_actions() -> step(), repeated,
+        would take, planned in one launch.  Returns a Routes -- .action(i) is
+        the i-th step()'s action batch, .steps the length; the last action
+        locks the piece in the slot.  A slot outside [0, n_slots), invalid or
+        unreachable gives steps 0 and every field 7.  need: a bool / uint8 [n]
+        mask; the envs it leaves out keep what `out` (a (route int64
+        [ROUTE_WORDS, n], steps int32 [n]) pair; fresh, uninitialised tensors
+        without it) held.  Reads the state, changes none of it."""
+        s = self._slots(slots)
+        nd = self._need(need)
+        route, steps = self._routes_out(out)
+        C.check(self._L.st_routes(self._ctx, _ptr(s), _ptr(nd), _ptr(route), _ptr(steps), self._stream()))
+        return Routes(route, steps)
+
+    def policy_routed(self, weights, features: str = "base", need=None, out=None) -> RoutedChoice:
+        """reachable(first=False) -> policy_linear(weights, features=...,
+        allowed=its steps) -> routes(its slots) in one launch
+        (st_policy_routed): the best slot the live piece can really reach, and
+        the whole route there.  Returns a RoutedChoice (slots, routes, scores);
+        no reachable candidate: slot -1, steps 0, score 0, every field 7.
+        need / out: as for routes(), out a (slots int32 [n], route, steps,
+        scores float32 [n]) tuple."""
+        fset = _feature_set(features)[0]
+        w = self._weights(weights, features)
+        nd = self._need(need)
+        if out is None:
+            sl = torch.empty(self.n, dtype=torch.int32, device=self.device)
+            sc = torch.empty(self.n, dtype=torch.float32, device=self.device)
+            route, steps = self._routes_out(None)
+        else:
+            sl, route, steps, sc = out
+            _check_tensor(sl, "out slots", (self.n,), (torch.int32,), self.device)
+            _check_tensor(sc, "out scores", (self.n,), (torch.float32,), self.device)
+            route, steps = self._routes_out((route, steps))
+        C.check(self._L.st_policy_routed(self._ctx, fset, _ptr(w), w.shape[0], _ptr(nd), _ptr(sl), _ptr(route),
+                                         _ptr(steps), _ptr(sc), self._stream()))
+        return RoutedChoice(sl, Routes(route, steps), sc)
+
+    def play_routed(self, weights, k: int, features: str = "base", returns: Optional[torch.Tensor] = None,
+                    episodes: Optional[torch.Tensor] = None, pieces: Optional[torch.Tensor] = None,
+                    obs: str = "packed"):
+        """k primitive steps of the honest feature player, enqueued by ONE
+        library call (st_play_routed): an env without a plan takes
+        policy_routed()'s slot and route, every env plays its route's next
+        action through the ordinary step -- every placement is one the
+        reference's own step can make.  Identical to that loop by hand; plans
+        do not outlive the call, and play_routed(a) then play_routed(b) equals
+        play_routed(a + b).  Adds rewards to `returns` (int64 [n]), dones to
+        `episodes` (int32 [n]) and the pieces whose route was played to its
+        last action to `pieces` (int32 [n]) -- continued, or fresh zeros -- and
+        returns (returns, episodes, pieces).  The last step's outputs are in
+        .reward, .done and (obs='packed') .obs.  Stream rule as play_linear."""
+        if obs not in ("packed", "none"):
+            raise ValueError("obs must be 'packed' or 'none'")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+            raise ValueError(f"k must be an integer >= 0, got {k!r}")
+        fset = _feature_set(features)[0]
+        w = self._weights(weights, features)
+        acc = []
+        for t, name, dt in ((returns, "returns", torch.int64), (episodes, "episodes", torch.int32),
+                            (pieces, "pieces", torch.int32)):
+            if t is None:
+                t = torch.zeros(self.n, dtype=dt, device=self.device)
+            else:
+                _check_tensor(t, name, (self.n,), (dt,), self.device)
+            acc.append(t)
+        C.check(self._L.st_play_routed(self._ctx, fset, _ptr(w), w.shape[0], int(k), _ptr(acc[0]), _ptr(acc[1]),
+                                       _ptr(acc[2]), _ptr(self.obs) if obs == "packed" else None, _ptr(self.reward),
+                                       _ptr(self.done), self._stream()))
+        return tuple(acc)
 
     # ------------------------------------------------------------ placement step
     def _placed_out(self, out) -> torch.Tensor:

@@ -40,8 +40,8 @@ extern "C" {
  * st_policy_linear / st_play_linear, st_place / st_step_placements /
  * st_play_linear_placements, st_reachable / st_route_actions and
  * st_feature_rows / st_afterstates_set / st_policy_linear_set /
- * st_play_linear_set, and st_next_piece / st_policy_lookahead /
- * st_play_lookahead.
+ * st_play_linear_set, st_next_piece / st_policy_lookahead /
+ * st_play_lookahead, and st_routes / st_policy_routed / st_play_routed.
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -710,6 +710,69 @@ int st_policy_lookahead(st_ctx *ctx, int32_t set, const float *d_weights1, const
 int st_play_lookahead(st_ctx *ctx, int32_t set, const float *d_weights1, const float *d_weights2,
                       int64_t n_w, float dead_value, int64_t k, int64_t *d_return, int32_t *d_episodes,
                       uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
+
+/* Routes: the whole shortest way of the live piece into a slot, and a player
+ * that plans it once a piece and plays it out under the reference's own step.
+ *
+ * For env e and slot s, in piece state x0 (the present piece word) with the
+ * board fixed: a0 = what st_route_actions answers for s in state x0, x1 = the
+ * piece state after step(a0) ("Reachability", 1. to 3.), a1 = st_route_actions's
+ * answer in x1, and so on -- well defined because after first[s] the target is
+ * steps[s] - 1 away.  The ROUTE of a reachable slot is (a0 .. a(n-1)) with
+ * n = steps[s]; its last action locks the piece in s.  Equivalently: with D(x)
+ * the length of the shortest sequence from x that locks at the slot's landing,
+ * a_i is the lowest-numbered action whose successor has D = D(x_i) - 1, for
+ * D = 1 the lowest-numbered action that locks there.
+ *
+ * Encoding: d_route is uint64 [ST_ROUTE_WORDS][n_envs]; action i sits at bits
+ * 3 * (i % 21) .. + 2 of word i / 21; bit 63 is 0.  Every field at or past the
+ * route's end holds 7, which no step takes as an action, so reading past the
+ * end is noticed.  A slot that cannot be served (outside [0, S), invalid or
+ * unreachable) gives all fields 7 and steps 0.  A route longer than
+ * ST_ROUTE_MAX keeps its first ST_ROUTE_MAX actions and reports its true length
+ * in d_steps: the caller plans again when the fields run out.  (No 4..32-wide
+ * board is known to produce one.)
+ *
+ * The three calls read and leave the state as st_reachable does, need no
+ * st_mt_sync, and a host-written piece word is read as st_reachable reads it.
+ * ST_EINVAL for a NULL ctx, a NULL required pointer, a bad set, n_w < 1 or
+ * max(lock_delay, 0) > ST_REACH_MAX_LOCK, ST_ESTATE before st_seed + st_reset,
+ * both before any GPU call. */
+#define ST_ROUTE_MAX 42   /* actions a packed route holds */
+#define ST_ROUTE_WORDS 2  /* its uint64 words: 21 actions each */
+/* The route to d_slots[e] (int32 [n_envs]) for every env with d_need[e] != 0
+ * (uint8 [n_envs]; NULL: every env); the words of the other envs in d_route /
+ * d_steps are left untouched.  d_steps int32 [n_envs] or NULL. */
+int st_routes(st_ctx *ctx, const int32_t *d_slots, const uint8_t *d_need, uint64_t *d_route, int32_t *d_steps,
+              st_stream stream);
+/* For the needed envs: d_slots[e] is what st_policy_linear_set(set, d_weights,
+ * n_w, d_allowed = st_reachable's d_steps) chooses, d_scores[e] its score,
+ * d_route / d_steps what st_routes gives for that slot -- one launch.  No
+ * candidate: slot -1, steps 0, score 0.0f, an all-7 route.  d_slots and d_route
+ * are required; d_steps and d_scores may be NULL. */
+int st_policy_routed(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w, const uint8_t *d_need,
+                     int32_t *d_slots, uint64_t *d_route, int32_t *d_steps, float *d_scores, st_stream stream);
+/* k primitive steps of the routed player from one host call, identical to
+ * this by hand: rem[e] = 0 for every env at the start of the call (plans are
+ * local to a call, so a state the host wrote between two calls never meets a
+ * stale plan); then k times: the envs with rem == 0 take st_policy_routed's
+ * slot and route and rem = min(steps, ST_ROUTE_MAX); a[e] = the env's next
+ * route action, or 2 where it has no route (as st_route_actions gives);
+ * rem = max(rem - 1, 0); the ordinary st_step on a.  d_return / d_episodes
+ * accumulate as in st_play_linear; d_pieces[e] (int32 [n_envs] or NULL) += 1 in
+ * every step that issues a route's last action.
+ * A call with k = a followed by one with k = b equals one call with k = a + b:
+ * planning again in the middle of a route finds the same slot, since the old
+ * target stays reachable and keeps its score while the reachable set only
+ * shrinks along a shortest route, and the rest of the route is the route from
+ * the state reached.
+ * The ring of reward / done rows and the sums, the first-call rule (see
+ * st_step_placements), the one-buffer-per-context ordering rule, both autoreset
+ * modes, k <= 0, the last step's d_obs / d_reward / d_done, not being gated and
+ * honouring the st_set_action_flag word are st_play_linear's. */
+int st_play_routed(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w, int64_t k, int64_t *d_return,
+                   int32_t *d_episodes, int32_t *d_pieces, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
+                   st_stream stream);
 
 /* Synthetic action source used by the benchmark and the parity tests:
  * d_out[e] = splitmix64(seed ^ ((t << 32) ^ (global_offset + e))) % 7. */
