@@ -775,6 +775,28 @@ int st_next_piece(st_ctx *c, uint8_t *d_next, st_stream stream) {
     return ST_OK;
 }
 
+int st_fork(st_ctx *dst, st_ctx *src, const int32_t *d_index, const uint8_t *d_mask, uint32_t flags,
+            st_stream stream) {
+    if (!dst || !src) return fail(ST_EINVAL, "st_fork: null context");
+    if (flags & ~(uint32_t)ST_FORK_KEEP_RNG) return fail(ST_EINVAL, "st_fork: unknown flag bits 0x%x", flags);
+    if (dst->cfg.width != src->cfg.width || dst->cfg.height != src->cfg.height)
+        return fail(ST_EINVAL, "st_fork: a %dx%d context from a %dx%d one", dst->cfg.width, dst->cfg.height,
+                    src->cfg.width, src->cfg.height);
+    if (dst->device != src->device)
+        return fail(ST_EINVAL, "st_fork: contexts on devices %d and %d", dst->device, src->device);
+    if (!dst->seeded || !dst->reset_once || !src->seeded || !src->reset_once)
+        return fail(ST_ESTATE, "st_fork before st_seed + st_reset of both contexts");
+    // the deep copy's grid: one wave per 64 envs (measured no slower than four, DESIGN.md "Fork"); DIAGNOSTIC
+    // (tools/fork_bench.py's A/B of the two): ST_FORK_WAVES=4 selects the other
+    int waves = 1;
+    if (const char *w = getenv("ST_FORK_WAVES")) waves = atoi(w) == 4 ? 4 : 1;
+    DeviceGuard g(dst->device);
+    if (!g.ok) return fail(ST_EHIP, "st_fork: hipSetDevice(%d) failed", dst->device);
+    ST_HIP(st::launch_fork(params(dst), params(src), d_index, d_mask, (flags & ST_FORK_KEEP_RNG) != 0, waves,
+                           (hipStream_t)stream));
+    return ST_OK;
+}
+
 int st_policy_lookahead(st_ctx *c, int32_t set, const float *d_weights1, const float *d_weights2, int64_t n_w,
                         float dead_value, const int32_t *d_allowed, int32_t *d_slots, int32_t *d_slots2,
                         uint8_t *d_actions, float *d_scores, float *d_scores_all, int32_t *d_slots2_all,

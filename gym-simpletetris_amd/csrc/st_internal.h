@@ -141,6 +141,11 @@ hipError_t launch_routes(const KParams &p, int set, const float *weights, int64_
 // pieces int32 [n] or null += 1 with a route's last action
 hipError_t launch_route_pop(const KParams &p, const uint64_t *route, const int32_t *steps, int32_t *rem, uint8_t *act,
                             int32_t *pieces, hipStream_t s);
+// st_fork: dst env e takes the state of src env index[e] (index int32 [dst.n] or null: e) where mask[e] != 0 (mask
+// uint8 [dst.n] or null: every env) and the index lies in [0, src.n); keep_rng: the MT19937 state stays dst's own.
+// waves: the deep copy's waves per 64 envs, 1 or 4
+hipError_t launch_fork(const KParams &dst, const KParams &src, const int32_t *index, const uint8_t *mask, bool keep_rng,
+                       int waves, hipStream_t s);
 hipError_t launch_grayscale(const KParams &p, const uint32_t *obs, int size, int channels,
                             int as_u8, void *out, hipStream_t s);
 hipError_t launch_unwire(int W, int H, int64_t n_global, int shards, int64_t n_cap, const uint32_t *wire,

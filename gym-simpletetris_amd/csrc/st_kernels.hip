@@ -17,7 +17,7 @@
 // each side are all-ones walls, so a collision test is four AND-tests with no
 // bounds checks and hard_drop is a count-trailing-zeros per piece column.
 //
-// Eight translation units are built from this file: the library's kernels (as
+// Nine translation units are built from this file: the library's kernels (as
 // it is); with ST_STEP_PACKED_TU defined (st_step_packed.hip), st_step's
 // packed-obs k_step instantiations (the prologue-draw schedule) and their
 // launcher alone -- in the library's own module they changed the code emitted
@@ -32,7 +32,8 @@
 // ST_LOOKAHEAD_TU defined (st_lookahead.hip), k_next_piece and
 // k_policy_lookahead's instantiations and their launchers alone; with
 // ST_ROUTES_TU defined (st_routes.hip), k_routes's instantiations, k_route_pop
-// and their launchers alone.  step_logic /
+// and their launchers alone; with ST_FORK_TU defined (st_fork.hip), k_fork's
+// instantiations and their launcher alone.  step_logic /
 // step_draw are shared source, but a second kernel instantiating them in ONE
 // module changes the code the compiler emits for k_step itself (it did: four
 // instructions around the lock ballot's LDS read); in a module of its own a
@@ -41,7 +42,7 @@
 #include "st_internal.h"
 
 #if defined(ST_STEP_EXPORT_TU) || defined(ST_STEP_PACKED_TU) || defined(ST_AFTERSTATES_TU) || defined(ST_REACHABLE_TU) || \
-    defined(ST_FEATURES_TU) || defined(ST_LOOKAHEAD_TU) || defined(ST_ROUTES_TU)
+    defined(ST_FEATURES_TU) || defined(ST_LOOKAHEAD_TU) || defined(ST_ROUTES_TU) || defined(ST_FORK_TU)
 #define ST_SIDE_TU 1  // not the library's own translation unit
 #endif
 #if defined(ST_AFTERSTATES_TU) || defined(ST_FEATURES_TU) || defined(ST_LOOKAHEAD_TU) || defined(ST_ROUTES_TU)
@@ -3495,6 +3496,7 @@ __global__ void k_seed(KParams p) {
     for (int x = 0; x < p.W; ++x) p.board[x * sd + e] = 0u;
     p.piece[e] = pack_piece(0, 0, p.W / 2, 0, 0);
 }
+#endif  // !ST_SIDE_TU
 
 // ---------------------------------------------------------------- MT sync
 // st_mt_sync: every env back to CPython's form (see "Double-buffered twist"):
@@ -3506,12 +3508,11 @@ __global__ void k_seed(KParams p) {
 // generation's progress restarts at 0, the preview is dropped: the next spawn
 // draws its piece, then a new preview).  One wave per 64 envs; it copies its
 // lanes' B buffers one env at a time, cooperatively.
-__global__ __launch_bounds__(kWave) void k_mt_sync(KParams p) {
-    const int lane = threadIdx.x;
-    const int64_t e0 = (int64_t)blockIdx.x * kWave;
-    const int64_t e = e0 + lane;
-    int32_t *row = p.stats + (int64_t)ST_STAT_MT_INDEX * p.stride;
-    const uint32_t r = (uint32_t)row[e];
+// mt_sync_lanes is the per-env part, shared with k_fork (st_fork.hip), which puts exactly the
+// envs it writes under ST_FORK_KEEP_RNG into that form: lane's env e0 + lane
+// has the index word r; the lanes with `on` get their generation into buffer A
+// (wave-uniform: every lane of the wave calls it); returns CPython's index.
+__device__ __forceinline__ int mt_sync_lanes(uint32_t *mt, int64_t e0, uint32_t r, bool on, int lane) {
     int idx = (int)(r & 0x3FFu);
     uint32_t cur = (r >> 20) & 1u;
     if (pv_ok(r)) {
@@ -3529,11 +3530,11 @@ __global__ __launch_bounds__(kWave) void k_mt_sync(KParams p) {
             cur ^= 1u;
         }
     }
-    uint64_t inb = __ballot(cur);
+    uint64_t inb = __ballot(on && cur);
     while (inb) {
         const int l = __builtin_ctzll(inb);
         inb &= inb - 1;
-        uint32_t *g = p.mt + (e0 + l) * kMtPitch;
+        uint32_t *g = mt + (e0 + l) * kMtPitch;
         uint32_t t[10];
 #pragma unroll
         for (int q = 0; q < 10; ++q) {
@@ -3546,6 +3547,17 @@ __global__ __launch_bounds__(kWave) void k_mt_sync(KParams p) {
             if (i < kMtN) g[i] = t[q];
         }
     }
+    return idx;
+}
+
+#ifndef ST_SIDE_TU
+__global__ __launch_bounds__(kWave) void k_mt_sync(KParams p) {
+    const int lane = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * kWave;
+    const int64_t e = e0 + lane;
+    int32_t *row = p.stats + (int64_t)ST_STAT_MT_INDEX * p.stride;
+    const uint32_t r = (uint32_t)row[e];
+    const int idx = mt_sync_lanes(p.mt, e0, r, true, lane);
     if (r != (uint32_t)idx) row[e] = idx;
 }
 
@@ -5578,6 +5590,114 @@ __global__ __launch_bounds__(256) void k_route_pop(int64_t n, const uint64_t *__
 }
 #endif  // ST_ROUTES_TU
 
+#ifdef ST_FORK_TU
+// ---------------------------------------------------------------- fork
+// st_fork: env e of p (dst) takes the state of env index[e] of f (src) --
+// copy.deepcopy of the TetrisEngine with random.getstate(), or with KEEP
+// (ST_FORK_KEEP_RNG) the engine alone while the env keeps its own stream.
+// One workgroup of WAVES waves per 64 dst envs.  Every wave reads the 64
+// indices and mask bytes (an env is WRITTEN iff it is real, masked in and its
+// index lies in [0, f.n): nothing else is ever read or stored, so padding envs
+// are neither sources nor targets).  Wave 0, lane = env, copies the W board
+// rows and the counter rows: the stores into dst's SoA rows are coalesced, the
+// loads gathers by index (one address for a broadcast).  Deep copy: the written
+// lanes' MT rows -- kMtPitch words: both generation buffers and the pad, so the
+// progress bits, a pending preview and its consumed-word count in the index
+// word stay true of them -- are then copied one env at a time, 16 B per lane
+// (kMtPitch * 4 = 316 * 16 B, every row base 16-B aligned), the written lanes
+// dealt round robin to the waves, each wave loading its next row before it
+// stores the present one.  (WAVES = 1 is the library's grid: four waves per
+// 64 envs measured no faster, DESIGN.md "Fork".)  KEEP: no MT row moves; the written envs are put into
+// CPython's form first (mt_sync_lanes: a preview they hold was drawn under the
+// old shape counts, tetris_env.py:183-191, so its words go back), which wave 0
+// does alone.
+struct ForkSrc {
+    const uint32_t *board;  // [W][stride]
+    const int32_t *stats;   // [ST_NSTAT][stride]
+    const uint32_t *mt;     // [stride][kMtPitch]
+    int64_t n, stride;
+    const int32_t *index;   // [p.n] or null: e
+    const uint8_t *mask;    // [p.n] or null: every env
+    int32_t same;           // f is p's own context: a deep copy of an env onto itself is skipped
+};
+constexpr int kMtRowQ = (int)(kMtPitch / 4);        // 16-B words of an MT row
+constexpr int kForkQ = (kMtRowQ + kWave - 1) / kWave;  // per lane
+static_assert(kMtPitch % 4 == 0, "MT rows are copied in 16-B accesses");
+
+template <int WAVES, bool KEEP>
+__global__ __launch_bounds__(WAVES *kWave) void k_fork(KParams p, ForkSrc f) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const int64_t e0 = (int64_t)blockIdx.x * kWave;
+    const int64_t e = e0 + lane;
+    const int64_t sd = p.stride, ss = f.stride;
+    bool wr = e < p.n && (f.mask == nullptr || f.mask[e] != 0);
+    int64_t s64 = e;
+    if (e < p.n && f.index) s64 = f.index[e];
+    wr = wr && s64 >= 0 && s64 < f.n;
+    if (!KEEP && f.same && s64 == e) wr = false;
+    const int s = wr ? (int)s64 : 0;  // (f.n <= 2^24)
+
+    [[maybe_unused]] int idx = 0;
+    if constexpr (KEEP) {
+        const uint32_t r = wr ? (uint32_t)p.stats[(int64_t)ST_STAT_MT_INDEX * sd + e] : 0u;
+        idx = mt_sync_lanes(p.mt, e0, r, wr, lane);
+    }
+    if (wave == 0 && wr) {
+        int32_t t[ST_NSTAT];
+#pragma unroll
+        for (int r = 0; r < ST_NSTAT; ++r)
+            t[r] = KEEP && r == ST_STAT_MT_INDEX ? idx : f.stats[(int64_t)r * ss + s];
+        for (int x0 = 0; x0 < p.W; x0 += 8) {
+            uint32_t b[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) b[j] = x0 + j < p.W ? f.board[(int64_t)(x0 + j) * ss + s] : 0u;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (x0 + j < p.W) p.board[(int64_t)(x0 + j) * sd + e] = b[j];
+        }
+#pragma unroll
+        for (int r = 0; r < ST_NSTAT; ++r) p.stats[(int64_t)r * sd + e] = t[r];
+    }
+    if constexpr (!KEEP) {
+        uint64_t m = __ballot(wr);
+        int turn = 0;
+        auto next = [&]() -> int {  // the wave's next written lane, or -1 (wave-uniform)
+            while (m) {
+                const int l = (int)__builtin_ctzll(m);
+                m &= m - 1;
+                if (turn++ % WAVES == wave) return l;
+            }
+            return -1;
+        };
+        auto load = [&](int l, u32x4(&v)[kForkQ]) {
+            const u32x4 *g = reinterpret_cast<const u32x4 *>(f.mt + (int64_t)__builtin_amdgcn_readlane(s, l) * kMtPitch);
+#pragma unroll
+            for (int q = 0; q < kForkQ; ++q) {
+                const int i = lane + kWave * q;
+                if (i < kMtRowQ) v[q] = g[i];
+            }
+        };
+        u32x4 a[kForkQ] = {}, b[kForkQ] = {};
+        int l = next();
+        if (l >= 0) load(l, a);
+        while (l >= 0) {
+            const int ln = next();
+            if (ln >= 0) load(ln, b);
+            u32x4 *g = reinterpret_cast<u32x4 *>(p.mt + (e0 + l) * kMtPitch);
+#pragma unroll
+            for (int q = 0; q < kForkQ; ++q) {
+                const int i = lane + kWave * q;
+                if (i < kMtRowQ) g[i] = a[q];
+            }
+#pragma unroll
+            for (int q = 0; q < kForkQ; ++q) a[q] = b[q];
+            l = ln;
+        }
+    }
+}
+#endif  // ST_FORK_TU
+
 }  // namespace
 
 // k_step's arguments: the preloaded six, then the whole KParams
@@ -5732,6 +5852,17 @@ hipError_t launch_route_pop(const KParams &p, const uint64_t *route, const int32
                             int32_t *pieces, hipStream_t s) {
     hipLaunchKernelGGL(k_route_pop, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p.n, route, steps, rem, act,
                        pieces);
+    return hipGetLastError();
+}
+#elif defined(ST_FORK_TU)
+hipError_t launch_fork(const KParams &dst, const KParams &src, const int32_t *index, const uint8_t *mask, bool keep_rng,
+                       int waves, hipStream_t s) {
+    const ForkSrc f{src.board, src.stats, src.mt, src.n, src.stride, index, mask, dst.stats == src.stats};
+    const dim3 grid((unsigned)(dst.stride / kWave));
+    if (keep_rng) hipLaunchKernelGGL((k_fork<1, true>), grid, dim3(kWave), 0, s, dst, f);
+    else if (waves == 1) hipLaunchKernelGGL((k_fork<1, false>), grid, dim3(kWave), 0, s, dst, f);
+    else if (waves == 4) hipLaunchKernelGGL((k_fork<4, false>), grid, dim3(4 * kWave), 0, s, dst, f);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 #elif defined(ST_STEP_PACKED_TU)

@@ -50,6 +50,7 @@ FEATURE_SETS = dict(base=0, bcts=1)  # st_feature_set
 FEATURE_NAMES = {"base": AFTER, "bcts": AFTER_BCTS}  # feature set -> its rows by name
 REACH_MAX_LOCK = 3  # ST_REACH_MAX_LOCK: the largest lock_delay st_reachable / st_route_actions take
 ROUTE_MAX, ROUTE_WORDS = 42, 2  # ST_ROUTE_MAX, ST_ROUTE_WORDS: a packed route's actions and uint64 words
+FORK_KEEP_RNG = 1 << 0  # st_fork_flags: ST_FORK_KEEP_RNG
 
 
 class StError(RuntimeError):
@@ -133,6 +134,7 @@ SIG = {
     "st_routes": ([_vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_policy_routed": ([_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_play_routed": ([_vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_fork": ([_vp, _vp, _vp, _vp, _u32, _vp], ctypes.c_int),
     "st_debug_stamps": ([_vp, _vp, _i64], ctypes.c_int),
     "st_last_error": ([], ctypes.c_char_p),
     "st_abi_version": ([], ctypes.c_int),
@@ -167,7 +169,8 @@ def load(path: str = LIB_PATH):
             if ab_override:
                 continue
             # an addition that did not change the ABI number (st_step_export, st_afterstates,
-            # st_policy_linear, st_place, st_reachable, st_afterstates_set, st_next_piece, st_routes):
+            # st_policy_linear, st_place, st_reachable, st_afterstates_set, st_next_piece, st_routes,
+            # st_fork):
             # the library on disk was built before it
             raise ImportError(f"{path}: no symbol {name} (a stale build of ABI {abi}: rebuild it with "
                               "`make -C gym-simpletetris_amd/csrc`)")

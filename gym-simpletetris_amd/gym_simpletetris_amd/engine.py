@@ -439,6 +439,7 @@ class TetrisBatch:
         self._place_act: Optional[torch.Tensor] = None  # placement_actions' reused output (made on first use)
         self._route_act: Optional[torch.Tensor] = None  # route_actions' reused output (made on first use)
         self.placed: Optional[torch.Tensor] = None  # place() / step_placements(): uint8 [n] commit flags (made on first use)
+        self._fork_groups: dict = {}  # fork_groups' (index, mask) device tensors by group size
         self._seeded = False
         if seeds is not None:
             self.seed(seeds)
@@ -812,6 +813,72 @@ class TetrisBatch:
         data = bytes(snapshot)
         with torch.cuda.device(self.device):
             C.check(self._L.st_load(self._ctx, data, len(data)))
+
+    # ------------------------------------------------------------ fork
+    def _fork_index(self, index):
+        """fork()'s index as a contiguous int32 device tensor [n]: a torch
+        tensor is checked (int32 [n] on the engine's device, never converted:
+        the kernel reads it through its raw pointer), anything else _intake
+        takes is converted from integers."""
+        if index is None:
+            return None
+        index = self._intake(index, (self.n,), "index")
+        if isinstance(index, torch.Tensor):
+            _check_tensor(index, "index", (self.n,), (torch.int32,), self.device)
+            return index
+        if index.dtype.kind not in "iu":
+            raise TypeError(f"index must be integers, got {index.dtype}")
+        if index.shape != (self.n,):
+            raise ValueError(f"index must have shape ({self.n},), got {index.shape}")
+        # (an index past int32 is out of every source's range: it stays so)
+        return torch.as_tensor(np.clip(index.astype(np.int64), -1, 2**31 - 1).astype(np.int32), device=self.device)
+
+    def fork(self, src: Optional["TetrisBatch"] = None, index=None, mask=None, keep_rng: bool = False):
+        """Copy env states on the device (st_fork): env e of this batch takes
+        the state of env index[e] of `src` (None: this batch itself) where
+        mask[e] is set -- the branching a rollout player, a beam search or a
+        population restart needs.  index: int32 [n] (None: e); mask: bool /
+        uint8 [n] (None: every env); device tensors, or host sequences.  An
+        index outside [0, src.n) leaves its env exactly as it is; so does a
+        cleared mask entry.  `src` may have another env count, lock_delay,
+        scoring flags and autoreset mode (configuration, not state) but the
+        same board size and device.
+        keep_rng=False is copy.deepcopy of the reference's TetrisEngine with
+        random.getstate(): board, piece, every counter row and the MT19937
+        state, so the copy then does what its source would have done.
+        keep_rng=True copies the engine without the random state: the env
+        keeps its own MT19937 stream (as sync_mt() shows it), so copies of
+        one game draw different piece futures.
+        In place (src is this batch) the result is defined iff no env written
+        with another env's state is itself the source of a written env --
+        fork_groups() is that pattern.  Asynchronous on the current stream, no
+        host read-back, no sync_mt() needed around it.  Returns the batch."""
+        idx = self._fork_index(index)
+        msk = self._need(mask)
+        src = self if src is None else src
+        if not isinstance(src, TetrisBatch):
+            raise TypeError(f"src must be a TetrisBatch, got {type(src)}")
+        if src.device != self.device:
+            raise ValueError(f"src is on {src.device}, this batch on {self.device}")
+        flags = C.FORK_KEEP_RNG if keep_rng else 0
+        with torch.cuda.device(self.device):
+            C.check(self._L.st_fork(self._ctx, src._ctx, _ptr(idx), _ptr(msk), flags, self._stream()))
+        return self
+
+    def fork_groups(self, group: int, keep_rng: bool = False):
+        """"R roots x B branches in one batch", in place: every env e takes the
+        state of its group's root (e // group) * group; the roots themselves
+        are not written.  fork() with an index and a mask cached per group
+        size."""
+        if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or group < 1:
+            raise ValueError(f"group must be an integer >= 1, got {group!r}")
+        cache = self._fork_groups
+        if group not in cache:
+            e = torch.arange(self.n, dtype=torch.int32, device=self.device)
+            root = e - e % int(group)
+            cache[group] = (root, (root != e).to(torch.uint8))
+        index, mask = cache[group]
+        return self.fork(None, index=index, mask=mask, keep_rng=keep_rng)
 
     def render_packed(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """TetrisEngine.render() (tetris_env.py:317-321): board + current piece,

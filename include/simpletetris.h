@@ -41,7 +41,8 @@ extern "C" {
  * st_play_linear_placements, st_reachable / st_route_actions and
  * st_feature_rows / st_afterstates_set / st_policy_linear_set /
  * st_play_linear_set, st_next_piece / st_policy_lookahead /
- * st_play_lookahead, and st_routes / st_policy_routed / st_play_routed.
+ * st_play_lookahead, st_routes / st_policy_routed / st_play_routed, and
+ * st_fork.
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -773,6 +774,56 @@ int st_policy_routed(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n
 int st_play_routed(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w, int64_t k, int64_t *d_return,
                    int32_t *d_episodes, int32_t *d_pieces, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
                    st_stream stream);
+
+/* Fork: env states copied on the device, between two contexts or inside one --
+ * what a rollout player, a beam search or a population restart needs to put one
+ * game into many envs and play on from there.
+ *
+ * For every env e of dst with d_mask[e] != 0 (uint8 [dst.n_envs]; NULL: every
+ * env), env e takes the state of env d_index[e] of src (int32 [dst.n_envs];
+ * NULL: d_index[e] = e).  An env whose index lies outside [0, src.n_envs) is
+ * left exactly as it is: nothing faults and nothing is reported.  The envs of
+ * dst that are not written keep every bit, src is only read, and padding envs
+ * are neither read nor written.
+ *
+ * flags == 0, the deep copy: in the reference's terms copy.deepcopy of the
+ *   TetrisEngine (tetris_env.py:125-335) together with random.getstate().
+ *   Board, piece word, all ST_NSTAT counter rows (the ST_STAT_EP_* rows
+ *   included) and the MT19937 state of dst env e are src env d_index[e]'s, in
+ *   the form st_mt_sync / st_save / st_export_env give it, and every later call
+ *   on dst env e (st_step*, st_rollout, st_next_piece, the policies) gives what
+ *   the same call on src env d_index[e] would give.  The engine-private part
+ *   travels too: the env's whole MT row -- both generation buffers, so the
+ *   next generation's progress and a pending preview with its consumed-word
+ *   count stay as they are in src.
+ * ST_FORK_KEEP_RNG, the engine without the random state: board, piece word and
+ *   every counter row except ST_STAT_MT_INDEX are copied as above (the shape
+ *   counts are counter rows); dst env e keeps its own MT19937 state, exactly as
+ *   st_mt_sync would show it before the call, so the copies of one game draw
+ *   different futures from their own streams.  A preview dst env e held was
+ *   drawn under its old shape counts (_choose_shape reads shape_counts,
+ *   tetris_env.py:183-191): it is dropped and its words are given back, which
+ *   leaves the written envs -- and only them -- in the form st_mt_sync gives.
+ *
+ * dst and src must have equal width and height and sit on the same device
+ * (ST_EINVAL otherwise); lock_delay, the scoring flags and the autoreset mode are
+ * configuration, not state, and may differ, as for st_load.  A copied lock
+ * counter above dst's max(lock_delay, 0) is a host-written lock counter above L
+ * ("Reachability") to the calls that read it.
+ * dst == src is allowed.  The result is defined iff no env that is written with
+ * the state of a DIFFERENT env is itself the source of another written env (a
+ * broadcast of group roots that are not written satisfies this by
+ * construction); otherwise the written envs' contents are unspecified, but
+ * they stay valid states: every index in range, nothing faults.
+ *
+ * Asynchronous on `stream`; the caller orders the work of both contexts on it.
+ * Not gated, consumes no gate, needs no st_mt_sync before or after, and leaves
+ * both contexts' play buffers alone.  ST_EINVAL for a NULL context, an unknown
+ * flag bit or mismatched contexts, ST_ESTATE unless both contexts are past
+ * st_seed + st_reset (or st_load); all before any GPU call. */
+enum st_fork_flags { ST_FORK_KEEP_RNG = 1u << 0 };
+int st_fork(st_ctx *dst, st_ctx *src, const int32_t *d_index, const uint8_t *d_mask,
+            uint32_t flags, st_stream stream);
 
 /* Synthetic action source used by the benchmark and the parity tests:
  * d_out[e] = splitmix64(seed ^ ((t << 32) ^ (global_offset + e))) % 7. */
