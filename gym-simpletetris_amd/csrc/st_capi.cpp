@@ -645,9 +645,11 @@ int st_policy_linear(st_ctx *c, const float *d_weights, int64_t n_w, int32_t *d_
 // set: the rows the policy scores (st_play_linear_set; the base set runs the two older kernels)
 // look: st_play_lookahead -- the policy is the two-ply kernel (d_weights its second-ply rows, look->weights1 its
 // first-ply rows or null), committing its own choice
+// look->expect: st_play_expect -- the same with the expectimax kernel (the odds of the next piece, not the piece)
 struct PlayLookahead {
     const float *weights1;
     float dead_value;
+    bool expect = false;
 };
 // routed: st_play_routed -- the planner for the envs whose plan has run out, then the pop of every env's next action
 struct PlayRouted {
@@ -685,7 +687,10 @@ static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weig
             ST_HIP(st::launch_routes(params(c), set, d_weights, n_w, nullptr, nullptr, q.plan_rem, q.plan_slot,
                                      q.plan_route, q.plan_steps, nullptr, s));
             ST_HIP(st::launch_route_pop(params(c), q.plan_route, q.plan_steps, q.plan_rem, q.act, routed->pieces, s));
-        } else if (look)
+        } else if (look && look->expect)
+            ST_HIP(st::launch_policy_expect(params(c), set, true, look->weights1, d_weights, n_w, look->dead_value,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s));
+        else if (look)
             ST_HIP(st::launch_policy_lookahead(params(c), set, true, look->weights1, d_weights, n_w, look->dead_value,
                                                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s));
         else if (set != ST_FEATS_BASE)
@@ -822,6 +827,41 @@ int st_play_lookahead(st_ctx *c, int32_t set, const float *d_weights1, const flo
                       int32_t *d_reward, uint8_t *d_done, st_stream stream) {
     const PlayLookahead look{d_weights1, dead_value};
     return play_impl(c, "st_play_lookahead", true, d_weights2, n_w, k, d_return, d_episodes, d_obs, d_reward, d_done,
+                     stream, set, &look);
+}
+
+int st_next_weights(st_ctx *c, int32_t *d_m, st_stream stream) {
+    if (!c || !d_m) return fail(ST_EINVAL, "st_next_weights: null argument");
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_next_weights before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_next_weights: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_next_weights(params(c), d_m, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_policy_expect(st_ctx *c, int32_t set, const float *d_weights1, const float *d_weights2, int64_t n_w,
+                     float dead_value, const int32_t *d_allowed, int32_t *d_slots, uint8_t *d_actions,
+                     float *d_scores, float *d_scores_all, float *d_tails, int32_t *d_slots2_all, st_stream stream) {
+    if (!c || !d_weights2) return fail(ST_EINVAL, "st_policy_expect: null argument");
+    if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS)
+        return fail(ST_EINVAL, "st_policy_expect: unknown feature set %d", set);
+    if (n_w < 1) return fail(ST_EINVAL, "st_policy_expect: n_w %lld < 1", (long long)n_w);
+    if (!d_slots && !d_actions && !d_scores && !d_scores_all && !d_tails && !d_slots2_all)
+        return fail(ST_EINVAL, "st_policy_expect: every output is null");
+    if (!std::isfinite(dead_value)) return fail(ST_EINVAL, "st_policy_expect: dead_value is not finite");
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_policy_expect before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_policy_expect: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_policy_expect(params(c), set, false, d_weights1, d_weights2, n_w, dead_value, d_allowed, d_slots,
+                                    d_actions, d_scores, d_scores_all, d_tails, d_slots2_all, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_play_expect(st_ctx *c, int32_t set, const float *d_weights1, const float *d_weights2, int64_t n_w,
+                   float dead_value, int64_t k, int64_t *d_return, int32_t *d_episodes, uint32_t *d_obs,
+                   int32_t *d_reward, uint8_t *d_done, st_stream stream) {
+    const PlayLookahead look{d_weights1, dead_value, true};
+    return play_impl(c, "st_play_expect", true, d_weights2, n_w, k, d_return, d_episodes, d_obs, d_reward, d_done,
                      stream, set, &look);
 }
 

@@ -120,6 +120,15 @@ hipError_t launch_policy_lookahead(const KParams &p, int set, bool commit, const
                                    const float *weights2, int64_t n_w, float dead_value, const int32_t *allowed,
                                    int32_t *slots, int32_t *slots2, uint8_t *actions, float *scores,
                                    float *scores_all, int32_t *slots2_all, hipStream_t s);
+// st_next_weights: m int32 [7][n], row i = 5 + max(counts) - counts[i] (st_expect.hip)
+hipError_t launch_next_weights(const KParams &p, int32_t *m, hipStream_t s);
+// st_policy_expect / st_play_expect (commit: the chosen first-ply slot is committed like launch_place): the expectimax
+// kernel over the rows of `set`, one launch, the MT row never read -- weights, allowed, slots, actions, scores and
+// scores_all as launch_policy_lookahead's; tails float [n][7][S], slots2_all int32 [n][7][S], any output null
+hipError_t launch_policy_expect(const KParams &p, int set, bool commit, const float *weights1, const float *weights2,
+                                int64_t n_w, float dead_value, const int32_t *allowed, int32_t *slots,
+                                uint8_t *actions, float *scores, float *scores_all, float *tails, int32_t *slots2_all,
+                                hipStream_t s);
 // st_play_linear: adds rows 0 .. rows - 1 of reward int32 [rows][n] / done uint8 [rows][n] to acc_return
 // int64 [n] / acc_episodes int32 [n] (either null) and copies the last row to out_reward / out_done (either null)
 hipError_t launch_play_sum(const KParams &p, const int32_t *reward, const uint8_t *done, int rows, int64_t *acc_return,

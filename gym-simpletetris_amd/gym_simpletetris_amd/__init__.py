@@ -10,7 +10,7 @@ is importable the ids are registered there too.
 import os as _os
 
 from .engine import (BCTS_WEIGHTS, DELLACHERIE_WEIGHTS, GREEDY_WEIGHTS, SHAPE_NAMES, Afterstates,  # noqa: F401
-                     LinearChoice, LookaheadChoice, Reachable, RoutedChoice, Routes, TetrisBatch, route_pack,
+                     ExpectChoice, LinearChoice, LookaheadChoice, Reachable, RoutedChoice, Routes, TetrisBatch, route_pack,
                      route_unpack)
 from .envs import TetrisEngine, TetrisEnv, TetrisVecEnv  # noqa: F401
 

@@ -131,6 +131,11 @@ SIG = {
                             ctypes.c_int),
     "st_play_lookahead": ([_vp, _i32, _vp, _vp, _i64, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
                           ctypes.c_int),
+    "st_next_weights": ([_vp, _vp, _vp], ctypes.c_int),
+    "st_policy_expect": ([_vp, _i32, _vp, _vp, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+                         ctypes.c_int),
+    "st_play_expect": ([_vp, _i32, _vp, _vp, _i64, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+                       ctypes.c_int),
     "st_routes": ([_vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_policy_routed": ([_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_play_routed": ([_vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
@@ -170,7 +175,7 @@ def load(path: str = LIB_PATH):
                 continue
             # an addition that did not change the ABI number (st_step_export, st_afterstates,
             # st_policy_linear, st_place, st_reachable, st_afterstates_set, st_next_piece, st_routes,
-            # st_fork):
+            # st_fork, st_next_weights):
             # the library on disk was built before it
             raise ImportError(f"{path}: no symbol {name} (a stale build of ABI {abi}: rebuild it with "
                               "`make -C gym-simpletetris_amd/csrc`)")

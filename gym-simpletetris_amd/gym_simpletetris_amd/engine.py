@@ -348,6 +348,21 @@ class LookaheadChoice:
         self.scores_all, self.slots2_all = scores_all, slots2_all
 
 
+class ExpectChoice:
+    """TetrisBatch.policy_expect()'s result: `slots` int32 [n] (the chosen
+    first-ply slot, -1: no candidate), `actions` uint8 [n] (as step() takes
+    them) and `scores` float32 [n]; with table=True also `scores_all` float32
+    [n, S] (every candidate's score, 0.0 elsewhere), `tails` float32 [n, 7, S]
+    (T_q(s1): the best second-ply score behind s1 for every piece q in
+    SHAPE_NAMES order, 0.0 elsewhere) and `slots2_all` int32 [n, 7, S] (that
+    piece's best second-ply slot, -1 where there is none), else None.  A field
+    not asked for (`out`) is None."""
+
+    def __init__(self, slots, actions, scores, scores_all=None, tails=None, slots2_all=None):
+        self.slots, self.actions, self.scores = slots, actions, scores
+        self.scores_all, self.tails, self.slots2_all = scores_all, tails, slots2_all
+
+
 def _dead_value(dead_value) -> float:
     """policy_lookahead's / play_lookahead's dead_value as a finite float."""
     if isinstance(dead_value, bool) or not isinstance(dead_value, (int, float, np.integer, np.floating)):
@@ -1413,6 +1428,99 @@ class TetrisBatch:
         C.check(self._L.st_play_lookahead(self._ctx, fset, _ptr(w1), _ptr(w2), w2.shape[0], dv, int(k),
                                           _ptr(returns), _ptr(episodes), _ptr(o_t) if obs == "packed" else None,
                                           _ptr(r_t), _ptr(d_t), self._stream()))
+        return returns, episodes
+
+    # ------------------------------------------------------------ next-piece odds, expectimax player
+    def next_weights(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The odds of the piece every env's next spawn takes
+        (st_next_weights): int32 [7, n], row i = 5 + max(counts) - counts[i]
+        over the env's shape counters -- m of _choose_shape()
+        (tetris_env.py:186), which picks shape i (SHAPE_NAMES order) with
+        probability m[i] / m.sum(0).  Unlike next_piece() this is what an agent
+        may know: the counters are info['statistics'] of every step.  Reads the
+        counters only and changes nothing.  `out`: an int32 [7, n] device
+        tensor to write."""
+        if out is None:
+            out = torch.empty((7, self.n), dtype=torch.int32, device=self.device)
+        else:
+            _check_tensor(out, "out", (7, self.n), (torch.int32,), self.device)
+        C.check(self._L.st_next_weights(self._ctx, _ptr(out), self._stream()))
+        return out
+
+    def policy_expect(self, weights, first_weights=None, dead_value: float = -1.0e6, features: str = "base",
+                      allowed=None, table: bool = False, out=None) -> ExpectChoice:
+        """policy_lookahead over the odds of the next piece instead of the
+        piece itself, in one launch (st_policy_expect): the two-ply player the
+        reference's rules allow, since it never reads the env's random state.
+        First ply, candidates, `allowed`, weights / first_weights, S1 and
+        dead_value are policy_lookahead's.  For a candidate s1 and every piece
+        q, T_q is the largest chain score over the valid placements of q on
+        s1's afterstate (ties to the lowest), or `dead_value` where s1 is dead
+        or q has no valid placement; with m = next_weights() of the env,
+        score(s1) = S1 + (sum_q float32(m[q]) * T_q) / float32(sum(m)), every
+        float32 operation rounded on its own, q in order 0..6.  The candidate
+        with the largest score wins, ties to the lowest slot.
+        Returns an ExpectChoice: .slots (-1: no candidate, then action 2, score
+        0), .actions, .scores, and with table=True .scores_all float32 [n, S],
+        .tails float32 [n, 7, S] and .slots2_all int32 [n, 7, S].  Changes
+        nothing, the engine's private preview included.  `out`: a (slots,
+        actions, scores) tuple -- with table=True (slots, actions, scores,
+        scores_all, tails, slots2_all) -- of device tensors to write; None
+        entries are not computed (at least one must be given)."""
+        n, S = self.n, self.n_slots
+        fset = _feature_set(features)[0]
+        w1, w2 = self._lookahead_weights(weights, first_weights, features)
+        dv = _dead_value(dead_value)
+        if isinstance(allowed, Reachable):
+            allowed = allowed.steps
+        if allowed is not None:
+            _check_tensor(allowed, "allowed", (n, S), (torch.int32,), self.device)
+        names = ("slots", "actions", "scores", "scores_all", "tails", "slots2_all")[: 6 if table else 3]
+        shapes = ((n,), (n,), (n,), (n, S), (n, 7, S), (n, 7, S))
+        dtypes = (torch.int32, torch.uint8, torch.float32, torch.float32, torch.float32, torch.int32)
+        if out is None:
+            out = tuple(torch.empty(sh, dtype=dt, device=self.device) for _, sh, dt in zip(names, shapes, dtypes))
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != len(names):
+                raise ValueError(f"out: a ({', '.join(names)}) tuple, None for an output not wanted")
+            if all(t is None for t in out):
+                raise ValueError("out: at least one output tensor is needed")
+            for t, name, sh, dt in zip(out, names, shapes, dtypes):
+                if t is not None:
+                    _check_tensor(t, "out " + name, sh, (dt,), self.device)
+        out = tuple(out) + (None,) * (6 - len(out))
+        C.check(self._L.st_policy_expect(self._ctx, fset, _ptr(w1), _ptr(w2), w2.shape[0], dv, _ptr(allowed),
+                                         *(_ptr(t) for t in out), self._stream()))
+        return ExpectChoice(*out)
+
+    def play_expect(self, weights, k: int, first_weights=None, dead_value: float = -1.0e6,
+                    features: str = "base", returns: Optional[torch.Tensor] = None,
+                    episodes: Optional[torch.Tensor] = None, obs: str = "packed", out=None):
+        """k pieces of policy_expect(weights, first_weights, dead_value) ->
+        step_placements(its slots), enqueued by ONE library call
+        (st_play_expect), identical to the k rounds by hand: play_lookahead
+        with the expectimax choice.  Every argument and the return value are
+        play_lookahead's."""
+        if obs not in ("packed", "none"):
+            raise ValueError("obs must be 'packed' or 'none'")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+            raise ValueError(f"k must be an integer >= 0, got {k!r}")
+        fset = _feature_set(features)[0]
+        w1, w2 = self._lookahead_weights(weights, first_weights, features)
+        dv = _dead_value(dead_value)
+        if returns is None:
+            returns = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        else:
+            _check_tensor(returns, "returns", (self.n,), (torch.int64,), self.device)
+        if episodes is None:
+            episodes = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        else:
+            _check_tensor(episodes, "episodes", (self.n,), (torch.int32,), self.device)
+        o_t, r_t, d_t = (self.obs, self.reward, self.done) if out is None \
+            else _check_out(out, self.width, self.n, self.device)
+        C.check(self._L.st_play_expect(self._ctx, fset, _ptr(w1), _ptr(w2), w2.shape[0], dv, int(k),
+                                       _ptr(returns), _ptr(episodes), _ptr(o_t) if obs == "packed" else None,
+                                       _ptr(r_t), _ptr(d_t), self._stream()))
         return returns, episodes
 
 

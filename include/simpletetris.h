@@ -41,8 +41,8 @@ extern "C" {
  * st_play_linear_placements, st_reachable / st_route_actions and
  * st_feature_rows / st_afterstates_set / st_policy_linear_set /
  * st_play_linear_set, st_next_piece / st_policy_lookahead /
- * st_play_lookahead, st_routes / st_policy_routed / st_play_routed, and
- * st_fork.
+ * st_play_lookahead, st_routes / st_policy_routed / st_play_routed,
+ * st_fork, and st_next_weights / st_policy_expect / st_play_expect.
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -711,6 +711,75 @@ int st_policy_lookahead(st_ctx *ctx, int32_t set, const float *d_weights1, const
 int st_play_lookahead(st_ctx *ctx, int32_t set, const float *d_weights1, const float *d_weights2,
                       int64_t n_w, float dead_value, int64_t k, int64_t *d_return, int32_t *d_episodes,
                       uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
+
+/* Next-piece odds.  d_m (int32 [7][n_envs], env innermost) row i is
+ * 5 + max_j counts[j] - counts[i] over the ST_STAT_COUNT0 .. +6 rows of the
+ * moment: exactly m of _choose_shape (tetris_env.py:186), every value >= 5.
+ * _choose_shape picks shape i with probability m[i] / sum(m), and
+ * shape_counts changes only at a spawn and is kept by clear() (st_next_piece's
+ * argument), so these are the odds of the piece the env's next _new_piece
+ * takes, behind a lock or behind a reset -- what an agent may know of it:
+ * shape_counts is info['statistics'] of every step.
+ * Reads the counter rows only and changes nothing, the engine-private preview
+ * included.  Not gated, consumes no gate, needs no st_mt_sync.  ST_EINVAL for a
+ * NULL ctx or d_m, ST_ESTATE before st_seed + st_reset, both before any GPU
+ * call. */
+int st_next_weights(st_ctx *ctx, int32_t *d_m, st_stream stream);
+
+/* Expectimax player: st_policy_lookahead over the odds of the next piece in
+ * place of the piece itself -- the two-ply player SimpleTetris-v0 allows (the
+ * reference shows no preview; st_next_piece reads the env's MT19937 state).
+ * First ply, word for word st_policy_lookahead's: the slots s1, their
+ *   validity and rows f1, the CANDIDATE rule and d_allowed, R =
+ *   st_feature_rows(set), the weight row e % n_w, S1(s1) (0.0f if d_weights1
+ *   is NULL), X(s1) (its board and its holes / piece_height counters), the
+ *   unfused float32 chain and ties to the lowest slot.
+ * Per-piece tail: for a candidate s1 and every piece q = 0..6 (shape_names
+ *   order), T_q(s1) = the largest chain score, with row e % n_w of d_weights2,
+ *   over the valid s2 of the rows st_afterstates_set(set) would return in
+ *   X(s1) with live piece q, ties to the lowest s2 -- if s1 is not dead and
+ *   some s2 is valid for q; otherwise T_q(s1) = dead_value and that piece's
+ *   best s2 is -1.
+ * Expectation: with m = st_next_weights of env e and M = sum of m[q] (an exact
+ *   integer sum), acc = 0.0f; for q = 0..6 in order acc = acc + (float)m[q] *
+ *   T_q(s1); E(s1) = acc / (float)M.  Every product, every sum and the one
+ *   division are rounded on their own (IEEE round-to-nearest-even; no fused
+ *   multiply-add).  The conversions of m and M are exact below 2^24: counts
+ *   that make a weight or the sum larger give an unspecified score, never a
+ *   fault.
+ * Score: score(s1) = S1(s1) + E(s1), one float32 add -- for a dead s1 too,
+ *   whose T_q are all dead_value: E is then the chain's value, which need not
+ *   be dead_value bit for bit.  Choice: the candidate with the largest score,
+ *   ties to the lowest s1.  No candidate: slot -1, action 2, score 0.0f.
+ *   Weights and dead_value must be finite (st_policy_lookahead's rule).
+ * Outputs, each may be NULL but not all six: d_slots int32 [n_envs]; d_actions
+ *   uint8 [n_envs], st_placement_actions's rule for the chosen s1; d_scores
+ *   float [n_envs]; d_scores_all float [n_envs][S], score(s1) for candidates,
+ *   0.0f elsewhere; d_tails float [n_envs][7][S], T_q(s1) for candidates, 0.0f
+ *   elsewhere; d_slots2_all int32 [n_envs][7][S], the best s2 per piece, -1
+ *   where there is none or the slot is no candidate.
+ * State: reads the board, the piece word and the counter rows; changes
+ *   nothing, the engine-private preview and both MT generation buffers
+ *   included; unlike st_policy_lookahead it draws no preview and never reads
+ *   the MT row: two contexts with the same boards, pieces and counters give
+ *   the same outputs whatever their seeds.  One launch.  Not gated, needs no
+ *   st_mt_sync.
+ * ST_EINVAL for a NULL ctx, NULL d_weights2, a bad set, n_w < 1, all six
+ * outputs NULL or a non-finite dead_value; ST_ESTATE before st_seed +
+ * st_reset; both before any GPU call. */
+int st_policy_expect(st_ctx *ctx, int32_t set, const float *d_weights1, const float *d_weights2,
+                     int64_t n_w, float dead_value, const int32_t *d_allowed, int32_t *d_slots,
+                     uint8_t *d_actions, float *d_scores, float *d_scores_all, float *d_tails,
+                     int32_t *d_slots2_all, st_stream stream);
+/* st_play_lookahead with st_policy_expect's choice: k times (st_policy_expect,
+ * d_allowed NULL, its chosen s1 committed by the same launch -> the step on
+ * the constant hard drop), identical to k rounds of st_policy_expect +
+ * st_step_placements(d_slots) by hand.  Everything else -- the ring and the
+ * sums, the first-call rule, the one-buffer-per-context rule, both autoreset
+ * modes, k <= 0, the outputs and the errors -- is st_play_lookahead's. */
+int st_play_expect(st_ctx *ctx, int32_t set, const float *d_weights1, const float *d_weights2,
+                   int64_t n_w, float dead_value, int64_t k, int64_t *d_return, int32_t *d_episodes,
+                   uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done, st_stream stream);
 
 /* Routes: the whole shortest way of the live piece into a slot, and a player
  * that plans it once a piece and plays it out under the reference's own step.
