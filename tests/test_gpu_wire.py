@@ -48,6 +48,8 @@ def pack_np(obs, rew, done, W, H):
     (10, 20, 513, dict(high_scoring=True, reward_step=True, penalise_holes=True, penalise_height=True)),
     (6, 9, 300, dict(penalise_holes=True, penalise_height=True, lock_delay=1, step_reset=True)),
     (32, 28, 130, dict(high_scoring=True)),
+    (7, 9, 130, dict(lock_delay=1)),        # 63 cells: done is bit 31 of the last word, no bit to spare
+    (8, 4, 130, dict(high_scoring=True)),   # 32 cells: the reward is word-aligned, done alone in its word
 ])
 def test_step_wire_equals_step(W, H, n, kw):
     import gym_simpletetris_amd as G
@@ -132,16 +134,37 @@ def test_step_wire_large_rewards_vs_oracle():
     assert big >= n // 2, big  # every env's first lock: |reward| > 2^15
 
 
-@pytest.mark.parametrize("n_global,shards", [(3 * 4096 + 2, 3), (1000, 8), (64, 1)])
-def test_unwire_shards_ragged(n_global, shards):
+def unpack_np(wire, W, H):
+    """pack_np's inverse: wire words [words][n] uint32 -> (obs [W][n] uint32,
+    H bits per column, reward int32 [n], done bool [n])."""
+    w = wire.astype(np.uint64)
+    bit = lambda i: (w[i // 32] >> np.uint64(i % 32)) & np.uint64(1)  # noqa: E731
+    obs = np.zeros((W, wire.shape[1]), np.uint64)
+    for x in range(W):
+        for y in range(H):
+            obs[x] |= bit(x * H + y) << np.uint64(y)
+    rew = np.zeros(wire.shape[1], np.uint64)
+    for b in range(32):
+        rew |= bit(W * H + b) << np.uint64(b)
+    return obs.astype(np.uint32), rew.astype(np.uint32).view(np.int32), bit(W * H + 32) != 0
+
+
+# 15x17: 255 cells, exactly 9 words; 7x9 and 8x4: test_step_wire_equals_step's alignments
+SHARD_CASES = [(n_global, shards, W, H) for W, H in ((10, 20), (7, 9), (8, 4), (15, 17), (32, 28))
+               for n_global, shards in ((3 * 4096 + 2, 3), (1000, 8), (64, 1))]
+
+
+@pytest.mark.parametrize("n_global,shards,W,H", SHARD_CASES,
+                         ids=[f"{n}-{s}" + ("" if (W, H) == (10, 20) else f"-{W}x{H}") for n, s, W, H in SHARD_CASES])
+def test_unwire_shards_ragged(n_global, shards, W, H):
     """st_unwire_shards on a gather's receive buffer [shards][words][n_cap]
     (shard_range's blocks, short shards zero-padded) == st_unwire of the
-    concatenated real columns."""
+    concatenated real columns == a numpy unpack of them."""
     from gym_simpletetris_amd import _lib as C
     from gym_simpletetris_amd.distributed import shard_cap, shard_range
     from gym_simpletetris_amd.engine import unwire, unwire_shards
-    W, H = 10, 20
     words = C.load().st_wire_words(W, H)
+    assert words == (W * H + 33 + 31) // 32
     cap = shard_cap(n_global, shards)
     g = torch.Generator().manual_seed(n_global)
     recv = torch.randint(-2**31, 2**31 - 1, (shards, words, cap), dtype=torch.int64, generator=g)
@@ -150,6 +173,10 @@ def test_unwire_shards_ragged(n_global, shards):
     eo, er, ed = unwire(cat, W, H)
     so, sr, sd = unwire_shards(recv, W, H, n_global)
     assert torch.equal(so, eo) and torch.equal(sr, er) and torch.equal(sd, ed)
+    no, nr, nd = unpack_np(cat.cpu().numpy().view(np.uint32), W, H)
+    assert np.array_equal(eo.cpu().numpy().view(np.uint32), no), "obs"
+    assert np.array_equal(er.cpu().numpy(), nr), "reward"
+    assert np.array_equal(ed.cpu().numpy(), nd), "done"
 
 
 def test_wire_abi_errors():
