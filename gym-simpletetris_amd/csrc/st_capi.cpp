@@ -41,8 +41,9 @@ struct st_ctx {
     // allocation made on first use (play_parts) -- a ring of reward rows int32
     // [R][n], the policy's actions uint8 [n], a ring of done rows uint8 [R][n],
     // the constant action 2 (hard drop) uint8 [n], filled then; behind them
-    // (8-byte aligned) st_play_routed's plans: route uint64 [ST_ROUTE_WORDS][n],
-    // slot, steps and rem int32 [n]
+    // (8-byte aligned) st_play_routed's / st_play_locks's plans: route uint64
+    // [ST_ROUTE_WORDS][n], slot (st_play_locks: lock position), steps and rem
+    // int32 [n]
     int32_t *play_buf;
 };
 
@@ -652,8 +653,10 @@ struct PlayLookahead {
     bool expect = false;
 };
 // routed: st_play_routed -- the planner for the envs whose plan has run out, then the pop of every env's next action
+// locks: st_play_locks -- the planner over every lock position (plan_slot then holds the chosen position)
 struct PlayRouted {
     int32_t *pieces;
+    bool locks = false;
 };
 static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weights, int64_t n_w, int64_t k,
                      int64_t *d_return, int32_t *d_episodes, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
@@ -684,8 +687,12 @@ static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weig
     for (int64_t i = 0; i < k; ++i) {
         const bool last = i == k - 1;
         if (routed) {
-            ST_HIP(st::launch_routes(params(c), set, d_weights, n_w, nullptr, nullptr, q.plan_rem, q.plan_slot,
-                                     q.plan_route, q.plan_steps, nullptr, s));
+            if (routed->locks)
+                ST_HIP(st::launch_locks(params(c), set, d_weights, n_w, nullptr, nullptr, q.plan_rem, q.plan_slot,
+                                        q.plan_route, q.plan_steps, nullptr, nullptr, nullptr, s));
+            else
+                ST_HIP(st::launch_routes(params(c), set, d_weights, n_w, nullptr, nullptr, q.plan_rem, q.plan_slot,
+                                         q.plan_route, q.plan_steps, nullptr, s));
             ST_HIP(st::launch_route_pop(params(c), q.plan_route, q.plan_steps, q.plan_rem, q.act, routed->pieces, s));
         } else if (look && look->expect)
             ST_HIP(st::launch_policy_expect(params(c), set, true, look->weights1, d_weights, n_w, look->dead_value,
@@ -903,6 +910,62 @@ int st_play_routed(st_ctx *c, int32_t set, const float *d_weights, int64_t n_w, 
                    st_stream stream) {
     const PlayRouted routed{d_pieces};
     return play_impl(c, "st_play_routed", false, d_weights, n_w, k, d_return, d_episodes, d_obs, d_reward, d_done,
+                     stream, set, nullptr, &routed);
+}
+
+int st_lock_set(st_ctx *c, uint32_t *d_rows, int32_t *d_pos, int64_t cap, int32_t *d_count, st_stream stream) {
+    if (const int rc = routes_check(c, "st_lock_set", d_rows || d_pos || d_count)) return rc;
+    if (d_pos && cap < 1) return fail(ST_EINVAL, "st_lock_set: cap %lld < 1", (long long)cap);
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_lock_set: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_lock_set(params(c), d_rows, d_pos, d_pos ? cap : 0, d_count, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_afterstates_at(st_ctx *c, int32_t set, const int32_t *d_pos, int64_t cap, int32_t *d_feat, uint32_t *d_boards,
+                      st_stream stream) {
+    if (!c || !d_pos || !d_feat) return fail(ST_EINVAL, "st_afterstates_at: null argument");
+    if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS)
+        return fail(ST_EINVAL, "st_afterstates_at: unknown feature set %d", set);
+    if (cap < 1) return fail(ST_EINVAL, "st_afterstates_at: cap %lld < 1", (long long)cap);
+    if (const int rc = routes_check(c, "st_afterstates_at", true)) return rc;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_afterstates_at: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_afterstates_at(params(c), set, d_pos, cap, d_feat, d_boards, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_routes_at(st_ctx *c, const int32_t *d_pos, const uint8_t *d_need, uint64_t *d_route, int32_t *d_steps,
+                 st_stream stream) {
+    if (const int rc = routes_check(c, "st_routes_at", d_pos && d_route)) return rc;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_routes_at: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_locks(params(c), -1, nullptr, 0, d_pos, d_need, nullptr, nullptr, d_route, d_steps, nullptr,
+                            nullptr, nullptr, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_policy_locks(st_ctx *c, int32_t set, const float *d_weights, int64_t n_w, const uint8_t *d_need, int32_t *d_pos,
+                    uint64_t *d_route, int32_t *d_steps, float *d_scores, int32_t *d_best, int32_t *d_count,
+                    st_stream stream) {
+    if (!c || !d_weights || !d_pos) return fail(ST_EINVAL, "st_policy_locks: null argument");
+    if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS)
+        return fail(ST_EINVAL, "st_policy_locks: unknown feature set %d", set);
+    if (n_w < 1) return fail(ST_EINVAL, "st_policy_locks: n_w %lld < 1", (long long)n_w);
+    if (const int rc = routes_check(c, "st_policy_locks", true)) return rc;
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_policy_locks: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_locks(params(c), set, d_weights, n_w, nullptr, d_need, nullptr, d_pos, d_route, d_steps, d_scores,
+                            d_best, d_count, (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_play_locks(st_ctx *c, int32_t set, const float *d_weights, int64_t n_w, int64_t k, int64_t *d_return,
+                  int32_t *d_episodes, int32_t *d_pieces, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
+                  st_stream stream) {
+    PlayRouted routed{d_pieces};
+    routed.locks = true;
+    return play_impl(c, "st_play_locks", false, d_weights, n_w, k, d_return, d_episodes, d_obs, d_reward, d_done,
                      stream, set, nullptr, &routed);
 }
 

@@ -150,6 +150,19 @@ hipError_t launch_routes(const KParams &p, int set, const float *weights, int64_
 // pieces int32 [n] or null += 1 with a route's last action
 hipError_t launch_route_pop(const KParams &p, const uint64_t *route, const int32_t *steps, int32_t *rem, uint8_t *act,
                             int32_t *pieces, hipStream_t s);
+// st_lock_set (st_locks.hip): rows uint32 [n][S], pos int32 [n][cap] (ascending, -1 behind the last), count int32 [n],
+// any null
+hipError_t launch_lock_set(const KParams &p, uint32_t *rows, int32_t *pos, int64_t cap, int32_t *count, hipStream_t s);
+// st_afterstates_at: pos int32 [n][cap] -> feat int32 [n][rows of set][cap], boards uint32 [n][W][cap] or null
+hipError_t launch_afterstates_at(const KParams &p, int set, const int32_t *pos, int64_t cap, int32_t *feat,
+                                 uint32_t *boards, hipStream_t s);
+// st_routes_at (set -1: the route to pos_in int32 [n]) / st_policy_locks / st_play_locks (set a feature set: the
+// planner over every lock position -- the chosen position to pos int32 [n], its score to scores, its rows to best
+// int32 [rows][n], the lock count to count int32 [n], each of the three or null; route null: the choice alone).
+// need, rem, route and steps as launch_routes's
+hipError_t launch_locks(const KParams &p, int set, const float *weights, int64_t n_w, const int32_t *pos_in,
+                        const uint8_t *need, int32_t *rem, int32_t *pos, uint64_t *route, int32_t *steps,
+                        float *scores, int32_t *best, int32_t *count, hipStream_t s);
 // st_fork: dst env e takes the state of src env index[e] (index int32 [dst.n] or null: e) where mask[e] != 0 (mask
 // uint8 [dst.n] or null: every env) and the index lies in [0, src.n); keep_rng: the MT19937 state stays dst's own.
 // waves: the deep copy's waves per 64 envs, 1 or 4

@@ -140,6 +140,11 @@ SIG = {
     "st_policy_routed": ([_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_play_routed": ([_vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_fork": ([_vp, _vp, _vp, _vp, _u32, _vp], ctypes.c_int),
+    "st_lock_set": ([_vp, _vp, _vp, _i64, _vp, _vp], ctypes.c_int),
+    "st_afterstates_at": ([_vp, _i32, _vp, _i64, _vp, _vp, _vp], ctypes.c_int),
+    "st_routes_at": ([_vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_policy_locks": ([_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_play_locks": ([_vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_debug_stamps": ([_vp, _vp, _i64], ctypes.c_int),
     "st_last_error": ([], ctypes.c_char_p),
     "st_abi_version": ([], ctypes.c_int),
@@ -175,7 +180,7 @@ def load(path: str = LIB_PATH):
                 continue
             # an addition that did not change the ABI number (st_step_export, st_afterstates,
             # st_policy_linear, st_place, st_reachable, st_afterstates_set, st_next_piece, st_routes,
-            # st_fork, st_next_weights):
+            # st_fork, st_next_weights, st_lock_set):
             # the library on disk was built before it
             raise ImportError(f"{path}: no symbol {name} (a stale build of ABI {abi}: rebuild it with "
                               "`make -C gym-simpletetris_amd/csrc`)")

@@ -161,6 +161,21 @@ def placement_rot_x(width: int, slot: int):
     return slot // (width + 6), slot % (width + 6) - 3
 
 
+def lock_pos(width: int, rot: int, x: int, y: int) -> int:
+    """The lock position (ST_LOCK_POS) of rotation `rot` at anchor (x, y) on a
+    board `width` wide: placement_slot(width, rot, x) * 32 + y, y in 0..31."""
+    if not 0 <= y < 32:
+        raise ValueError(f"y {y} outside 0..31")
+    return placement_slot(width, rot, x) * 32 + y
+
+
+def lock_rot_x_y(width: int, pos: int):
+    """lock_pos's inverse: (rot, x, y) of a position in [0, 32 * 4 * (width + 6))."""
+    if pos < 0:
+        raise ValueError(f"pos {pos} < 0")
+    return placement_rot_x(width, pos >> 5) + (pos & 31,)
+
+
 def _row_names(rows: int):
     """The rows by name of a feature tensor with `rows` rows: _lib.AFTER, or
     _lib.AFTER_BCTS where it holds the 18 rows of features='bcts'."""
@@ -261,6 +276,33 @@ class RoutedChoice:
 
     def __iter__(self):
         return iter((self.slots, self.routes, self.scores))
+
+
+class LockSet:
+    """TetrisBatch.lock_set()'s result: `rows` int32 [n, S] (bit y of word
+    (e, s): the piece locks at row y of slot s; None with rows=False), `pos`
+    int32 [n, cap] (the env's lock positions, ascending, -1 behind the last;
+    None without a cap) and `count` int32 [n], the true count."""
+
+    def __init__(self, rows, pos, count):
+        self.rows, self.pos, self.count = rows, pos, count
+
+
+class LockChoice:
+    """TetrisBatch.policy_locks()'s result: `pos` int32 [n] (-1: no lock
+    position), `routes` (a Routes), `scores` float32 [n], `feat` int32
+    [rows, n] (the chosen position's feature rows, by name as LinearChoice's)
+    and `count` int32 [n], the env's lock positions."""
+
+    def __init__(self, pos, routes, scores, feat, count):
+        self.pos, self.routes, self.scores, self.feat, self.count = pos, routes, scores, feat, count
+
+    def __getattr__(self, name):  # (only names not found otherwise)
+        feat = None if name == "feat" else self.feat
+        row = None if feat is None else _row_names(feat.shape[0]).get(name)
+        if row is None:
+            raise AttributeError(name)
+        return feat[row]
 
 
 # st_policy_greedy's score as linear feature weights: 80 * lines - 12 * holes
@@ -1161,6 +1203,143 @@ class TetrisBatch:
         C.check(self._L.st_play_routed(self._ctx, fset, _ptr(w), w.shape[0], int(k), _ptr(acc[0]), _ptr(acc[1]),
                                        _ptr(acc[2]), _ptr(self.obs) if obs == "packed" else None, _ptr(self.reward),
                                        _ptr(self.done), self._stream()))
+        return tuple(acc)
+
+    # ------------------------------------------------------------ lock positions
+    def lock_set(self, rows: bool = True, cap: Optional[int] = None, out=None) -> LockSet:
+        """Every (rot, x, y) each env's live piece can be locked at under the
+        reference's step, the tucks under overhangs that are no slot's landing
+        included (st_lock_set).  Returns a LockSet: `rows` int32 [n, S], bit y
+        of word (e, s) set iff the piece locks collision-free at row y of slot
+        s (rows=False: None); with `cap`, `pos` int32 [n, cap], the positions
+        lock_pos(rot, x, y) = slot * 32 + y in ascending order, -1 behind the
+        last, a longer list cut; `count` int32 [n], the true count.  Reads the
+        state, changes none of it; lock_delay above REACH_MAX_LOCK is refused.
+        `out`: a (rows, pos, count) triple of device tensors to write (rows /
+        pos None where not asked for)."""
+        n, S = self.n, self.n_slots
+        if cap is not None and (isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 1):
+            raise ValueError(f"cap must be an integer >= 1, got {cap!r}")
+        if out is None:
+            rw = torch.empty((n, S), dtype=torch.int32, device=self.device) if rows else None
+            ps = torch.empty((n, int(cap)), dtype=torch.int32, device=self.device) if cap is not None else None
+            cnt = torch.empty(n, dtype=torch.int32, device=self.device)
+        else:
+            rw, ps, cnt = out
+            if rows:
+                _check_tensor(rw, "out rows", (n, S), (torch.int32,), self.device)
+            elif rw is not None:
+                raise ValueError("out rows given with rows=False")
+            if cap is not None:
+                _check_tensor(ps, "out pos", (n, int(cap)), (torch.int32,), self.device)
+            elif ps is not None:
+                raise ValueError("out pos given without cap")
+            _check_tensor(cnt, "out count", (n,), (torch.int32,), self.device)
+        C.check(self._L.st_lock_set(self._ctx, _ptr(rw), _ptr(ps), int(cap) if cap is not None else 0, _ptr(cnt),
+                                    self._stream()))
+        return LockSet(rw, ps, cnt)
+
+    def _positions(self, pos, shape, name="pos") -> torch.Tensor:
+        """Lock positions as a contiguous int32 device tensor of `shape` (None:
+        any extent): a device int32 tensor as it is, another integer tensor or
+        a host array converted."""
+        if isinstance(pos, torch.Tensor):
+            if pos.is_floating_point() or pos.is_complex() or pos.dtype == torch.bool:
+                raise TypeError(f"{name} must be integers, got {pos.dtype}")
+            q = pos.to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            q = torch.as_tensor(np.ascontiguousarray(np.asarray(pos).astype(np.int32)), device=self.device)
+        if len(q.shape) != len(shape) or any(w is not None and w != g for w, g in zip(shape, q.shape)):
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(q.shape)}")
+        return q
+
+    def afterstates_at(self, pos, boards: bool = True, features: str = "base") -> Afterstates:
+        """afterstates() at given lock positions (st_afterstates_at): pos int32
+        [n, cap], any order and any values.  Entry (e, i) is evaluable iff it
+        decodes to a slot and a row y < height, the piece is collision-free at
+        (x, y) and occupied at (x, y + 1); its rows and board are those of
+        afterstates(features=...) with the piece set at (x, y) in place of the
+        hard drop from row 0 (.y = y).  Every row and the board of any other
+        entry, -1 included, is 0.  Returns an Afterstates with feat int32
+        [n, rows, cap] and boards int32 [n, W, cap] (or None).  Reads the state,
+        changes none of it."""
+        fset, nrows, _ = _feature_set(features)
+        q = self._positions(pos, (self.n, None))
+        cap = q.shape[1]
+        if cap < 1:
+            raise ValueError("pos: no entries")
+        feat = torch.empty((self.n, nrows, cap), dtype=torch.int32, device=self.device)
+        brd = torch.empty((self.n, self.width, cap), dtype=torch.int32, device=self.device) if boards else None
+        C.check(self._L.st_afterstates_at(self._ctx, fset, _ptr(q), cap, _ptr(feat), _ptr(brd), self._stream()))
+        return Afterstates(feat, brd)
+
+    def routes_at(self, pos, need=None, out=None) -> Routes:
+        """routes() with a lock position per env as the target (st_routes_at):
+        the shortest action sequence that locks the live piece exactly at
+        lock_rot_x_y(pos[e]).  A position that is -1, does not decode or is no
+        lock position gives steps 0 and every field 7.  need / out: as for
+        routes()."""
+        q = self._positions(pos, (self.n,))
+        nd = self._need(need)
+        route, steps = self._routes_out(out)
+        C.check(self._L.st_routes_at(self._ctx, _ptr(q), _ptr(nd), _ptr(route), _ptr(steps), self._stream()))
+        return Routes(route, steps)
+
+    def policy_locks(self, weights, features: str = "base", need=None, out=None) -> LockChoice:
+        """lock_set() -> afterstates_at(its list) -> the linear score of
+        policy_linear(weights, features=...) -> routes_at(the best) in one
+        launch (st_policy_locks): the best place the live piece can really be
+        locked at, tucks included, ties to the lowest position, and the whole
+        route there.  Returns a LockChoice (pos, routes, scores, feat, count);
+        no lock position: pos -1, steps 0, score 0, zero feat column, every
+        field 7.  need: as for routes(); out: a (pos int32 [n], route, steps,
+        scores float32 [n], feat int32 [rows, n], count int32 [n]) tuple."""
+        fset, nrows, _ = _feature_set(features)
+        w = self._weights(weights, features)
+        nd = self._need(need)
+        if out is None:
+            ps = torch.empty(self.n, dtype=torch.int32, device=self.device)
+            sc = torch.empty(self.n, dtype=torch.float32, device=self.device)
+            ft = torch.empty((nrows, self.n), dtype=torch.int32, device=self.device)
+            cnt = torch.empty(self.n, dtype=torch.int32, device=self.device)
+            route, steps = self._routes_out(None)
+        else:
+            ps, route, steps, sc, ft, cnt = out
+            _check_tensor(ps, "out pos", (self.n,), (torch.int32,), self.device)
+            _check_tensor(sc, "out scores", (self.n,), (torch.float32,), self.device)
+            _check_tensor(ft, "out feat", (nrows, self.n), (torch.int32,), self.device)
+            _check_tensor(cnt, "out count", (self.n,), (torch.int32,), self.device)
+            route, steps = self._routes_out((route, steps))
+        C.check(self._L.st_policy_locks(self._ctx, fset, _ptr(w), w.shape[0], _ptr(nd), _ptr(ps), _ptr(route),
+                                        _ptr(steps), _ptr(sc), _ptr(ft), _ptr(cnt), self._stream()))
+        return LockChoice(ps, Routes(route, steps), sc, ft, cnt)
+
+    def play_locks(self, weights, k: int, features: str = "base", returns: Optional[torch.Tensor] = None,
+                   episodes: Optional[torch.Tensor] = None, pieces: Optional[torch.Tensor] = None,
+                   obs: str = "packed"):
+        """play_routed() with policy_locks() as the planner (st_play_locks): k
+        primitive steps of the feature player over every lock position, tucks
+        under overhangs included, enqueued by ONE library call.  Identical to
+        the loop by hand; plans do not outlive the call, and play_locks(a)
+        then play_locks(b) equals play_locks(a + b).  returns / episodes /
+        pieces, the result and the stream rule are play_routed's."""
+        if obs not in ("packed", "none"):
+            raise ValueError("obs must be 'packed' or 'none'")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+            raise ValueError(f"k must be an integer >= 0, got {k!r}")
+        fset = _feature_set(features)[0]
+        w = self._weights(weights, features)
+        acc = []
+        for t, name, dt in ((returns, "returns", torch.int64), (episodes, "episodes", torch.int32),
+                            (pieces, "pieces", torch.int32)):
+            if t is None:
+                t = torch.zeros(self.n, dtype=dt, device=self.device)
+            else:
+                _check_tensor(t, name, (self.n,), (dt,), self.device)
+            acc.append(t)
+        C.check(self._L.st_play_locks(self._ctx, fset, _ptr(w), w.shape[0], int(k), _ptr(acc[0]), _ptr(acc[1]),
+                                      _ptr(acc[2]), _ptr(self.obs) if obs == "packed" else None, _ptr(self.reward),
+                                      _ptr(self.done), self._stream()))
         return tuple(acc)
 
     # ------------------------------------------------------------ placement step

@@ -42,7 +42,9 @@ extern "C" {
  * st_feature_rows / st_afterstates_set / st_policy_linear_set /
  * st_play_linear_set, st_next_piece / st_policy_lookahead /
  * st_play_lookahead, st_routes / st_policy_routed / st_play_routed,
- * st_fork, and st_next_weights / st_policy_expect / st_play_expect.
+ * st_fork, st_next_weights / st_policy_expect / st_play_expect, and
+ * st_lock_set / st_afterstates_at / st_routes_at / st_policy_locks /
+ * st_play_locks.
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -417,7 +419,8 @@ int st_placement_actions(st_ctx *ctx, const int32_t *d_slots, uint8_t *d_actions
  * It follows that after first[s] the target is steps[s] - 1 away, and that
  * locking there leaves exactly that slot's afterstate board and, in that step,
  * its ST_AFTER_REWARD.  Lock positions that are no slot's landing (a tuck under
- * an overhang) are outside the slot set and are not reported.
+ * an overhang) are outside the slot set and are not reported here: "Lock
+ * positions" below reports, evaluates and routes them.
  *
  * Both calls follow st_afterstates: they read the state enqueued before them
  * on `stream` and change none of it (board, piece, counters, MT, preview), need
@@ -843,6 +846,95 @@ int st_policy_routed(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n
 int st_play_routed(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w, int64_t k, int64_t *d_return,
                    int32_t *d_episodes, int32_t *d_pieces, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
                    st_stream stream);
+
+/* Lock positions: every place the live piece can be locked at, the tucks under
+ * overhangs that are no slot's landing included -- their set, their afterstate
+ * rows, the routes into them, a linear player over all of them and its play
+ * loop.
+ *
+ * A LOCK POSITION of env e is a triple (rot, x, y) such that
+ *  - some action sequence from the env's present piece state locks the piece at
+ *    rotation rot, anchor (x, y), under the three rules of "Reachability"
+ *    (action, gravity, lock counter), the board fixed and
+ *    L = max(lock_delay, 0) <= ST_REACH_MAX_LOCK, and
+ *  - the piece is collision-free there: not is_occupied(cells, (x, y), board)
+ *    (tetris_env.py:29-36).
+ * A start that collides and locks where it stands (a spawn onto the stack) is
+ * therefore no lock position.  A lock position is always grounded (is_occupied
+ * at (x, y + 1)) and has 0 <= x < W, 0 <= y < H.  Slot s of st_afterstates is
+ * reachable (st_reachable: steps > 0) iff (rot_s, x_s, ST_AFTER_Y[s]) is a lock
+ * position.
+ *
+ * Encoding: pos = slot * 32 + y (int32), slot = rot * (W + 6) + (x + 3) as
+ * everywhere; -1: none.  The numeric order of pos is the order of choice:
+ * lowest slot, then lowest row.
+ *
+ * A position is EVALUABLE iff pos decodes to a slot in [0, S) and a row y < H,
+ * the piece is collision-free at (x, y) in rot and is occupied at (x, y + 1).
+ * Evaluation does not depend on reachability.
+ *
+ * The five calls read and leave the state as st_reachable does (they read the
+ * state enqueued before them on `stream` and change none of it -- st_play_locks
+ * steps, as st_play_routed does), need no st_mt_sync, are not gated and consume
+ * no gate, and a host-written piece word is read as st_reachable reads it.
+ * ST_EINVAL for a NULL ctx, a NULL required pointer, a bad set, n_w < 1, a cap
+ * < 1 where a list is passed, or max(lock_delay, 0) > ST_REACH_MAX_LOCK (all
+ * five calls); ST_ESTATE before st_seed + st_reset; both before any GPU call. */
+#define ST_LOCK_POS(slot, y) ((slot) * 32 + (y))
+#define ST_LOCK_SLOT(pos) ((pos) >> 5)
+#define ST_LOCK_Y(pos) ((pos) & 31)
+/* d_rows uint32 [n_envs][S] or NULL: bit y of word (e, s) is set iff
+ * (rot_s, x_s, y) is a lock position.  d_pos int32 [n_envs][cap] or NULL: the
+ * env's lock positions in ascending pos order, padded with -1; a list longer
+ * than cap is cut to its first cap entries (cap >= 1 with a non-NULL d_pos).
+ * d_count int32 [n_envs] or NULL: the true count, cut or not.  Not all three
+ * may be NULL.  A start outside the lane grid, which st_reachable answers with
+ * "reaches no slot", gives an empty set. */
+int st_lock_set(st_ctx *ctx, uint32_t *d_rows, int32_t *d_pos, int64_t cap, int32_t *d_count, st_stream stream);
+/* d_pos int32 [n_envs][cap], any order, any values; d_feat int32
+ * [n_envs][rows][cap], rows = st_feature_rows(set); d_boards uint32
+ * [n_envs][W][cap] or NULL.  For an evaluable position the rows are those of
+ * st_afterstates_set with the piece set at (x, y) in place of the hard drop
+ * from row 0: ST_AFTER_Y = y, the piece set with _set_piece's clipping, then
+ * _clear_lines, ST_AFTER_REWARD from the env's holes and piece_height counters
+ * under the context's flags, the seven BCTS rows from the piece's cells at
+ * (x + i, y + j); the board is the board after the clear, before any death
+ * erase.  Every row and the board of a non-evaluable entry, -1 included, is 0
+ * (ST_AFTER_VALID too).  At pos = ST_LOCK_POS(s, ST_AFTER_Y[s]) of a valid
+ * slot the rows and board equal st_afterstates_set's for s bit for bit. */
+int st_afterstates_at(st_ctx *ctx, int32_t set, const int32_t *d_pos, int64_t cap, int32_t *d_feat,
+                      uint32_t *d_boards, st_stream stream);
+/* st_routes with the target (rot, x, y) of d_pos[e] in place of a slot's
+ * landing: D(x) is the length of the shortest sequence that locks exactly
+ * there.  Encoding, ST_ROUTE_MAX, d_need and the all-7 / steps 0 answer for a
+ * position that cannot be served (-1, undecodable, or no lock position) are
+ * st_routes's. */
+int st_routes_at(st_ctx *ctx, const int32_t *d_pos, const uint8_t *d_need, uint64_t *d_route, int32_t *d_steps,
+                 st_stream stream);
+/* For the needed envs, one launch: the lock set as st_lock_set gives it; every
+ * lock position's rows as st_afterstates_at gives them; the unfused float32
+ * chain of st_policy_linear_set with weight row e % n_w; d_pos[e] = the lock
+ * position with the largest score, ties to the lowest pos; d_route / d_steps
+ * what st_routes_at gives for it.  d_pos is required.  d_route may be NULL:
+ * the backward search and the walk are then skipped, and d_steps is not
+ * written.  d_steps, d_scores (float [n_envs]), d_best (int32 [rows][n_envs],
+ * the chosen position's rows) and d_count (int32 [n_envs], the lock count) may
+ * be NULL.  No lock position: pos -1, steps 0, score 0.0f, a zero d_best
+ * column, an all-7 route.  Envs that are not needed keep their words. */
+int st_policy_locks(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w, const uint8_t *d_need,
+                    int32_t *d_pos, uint64_t *d_route, int32_t *d_steps, float *d_scores, int32_t *d_best,
+                    int32_t *d_count, st_stream stream);
+/* st_play_routed word for word, with st_policy_locks as the planner: the rem
+ * rule, plans local to a call, d_pieces, the ring and the sums, the first-call
+ * rule, the one-buffer-per-context rule, both autoreset modes and k <= 0.
+ * A call with k = a followed by one with k = b equals one call with k = a + b,
+ * by st_play_routed's argument: the lock set only shrinks along a shortest
+ * route, the old target stays in it and keeps its score (the board does not
+ * move before the lock), ties go to the lowest pos, and the rest of the route
+ * is the route from the state reached. */
+int st_play_locks(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w, int64_t k, int64_t *d_return,
+                  int32_t *d_episodes, int32_t *d_pieces, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
+                  st_stream stream);
 
 /* Fork: env states copied on the device, between two contexts or inside one --
  * what a rollout player, a beam search or a population restart needs to put one
