@@ -1,6 +1,6 @@
 // st_kernels.hip -- MI355X (gfx950) kernels of the batched SimpleTetris engine.
 //
-// Hot path: TetrisEngine.step (/root/reference/gym_simpletetris/envs/tetris_env.py:243-304)
+// Hot path: TetrisEngine.step (the reference's gym_simpletetris/envs/tetris_env.py:243-304)
 // for N independent envs, one env per lane, one wave (64 envs) per workgroup.
 //
 // Data layout (HBM, SoA over envs, row stride = padded env count):
@@ -17,44 +17,34 @@
 // each side are all-ones walls, so a collision test is four AND-tests with no
 // bounds checks and hard_drop is a count-trailing-zeros per piece column.
 //
-// Ten translation units are built from this file: the library's kernels (as
-// it is); with ST_STEP_PACKED_TU defined (st_step_packed.hip), st_step's
-// packed-obs k_step instantiations (the prologue-draw schedule) and their
-// launcher alone -- in the library's own module they changed the code emitted
-// for the float32 k_step, which keeps the parent schedule and, apart from
-// them, its instruction stream; with ST_STEP_EXPORT_TU defined
-// (st_step_export.hip), k_step_export and its launcher alone; with ST_AFTERSTATES_TU defined (st_afterstates.hip),
-// k_afterstates, k_placement_actions, k_place, k_policy_linear, k_play_sum and
-// their launchers alone; with ST_REACHABLE_TU defined (st_reachable.hip),
-// k_reachable's instantiations and their launchers alone; with
-// ST_FEATURES_TU defined (st_features.hip), the extended-feature-set kernels
-// (k_afterstates_set, k_policy_linear_set) and their launchers alone; with
-// ST_LOOKAHEAD_TU defined (st_lookahead.hip), k_next_piece and
-// k_policy_lookahead's instantiations and their launchers alone; with
-// ST_ROUTES_TU defined (st_routes.hip), k_routes's instantiations, k_route_pop
-// and their launchers alone; with ST_FORK_TU defined (st_fork.hip), k_fork's
-// instantiations and their launcher alone; with ST_EXPECT_TU defined
-// (st_expect.hip), k_next_weights and k_policy_expect's instantiations and
-// their launchers alone; with ST_LOCKS_TU defined (st_locks.hip), k_lock_set,
-// k_afterstates_at's and k_locks's instantiations and their launchers alone.
-// step_logic /
-// step_draw are shared source, but a second kernel instantiating them in ONE
-// module changes the code the compiler emits for k_step itself (it did: four
-// instructions around the lock ballot's LDS read); in a module of its own a
-// new kernel cannot touch the code objects of k_step, k_rollout and
-// k_rollout2.
+//
+// Translation units.  A second kernel that instantiates step_logic / step_draw
+// in ONE module changes the code the compiler emits for k_step itself (it did:
+// four instructions around the lock ballot's LDS read), so every later kernel
+// family is a module of its own, where it cannot touch the code objects of
+// k_step, k_rollout and k_rollout2.  This file is the core every unit is
+// compiled from -- the piece table, the column / LDS / buffer / lock / MT / draw
+// helpers, the step and rollout waves -- and, under the one switch
+// `#ifndef ST_SIDE_TU`, the library's own kernels and launchers.  A side unit
+// defines ST_SIDE_TU, includes this file and holds its own text; what several
+// side units share and the core does not need is in st_eval.h (slot
+// evaluators, column staging, score, reductions) and st_search.h (the bit-set
+// search helpers).
+//   unit                kernels
+//   st_kernels.hip      k_seed, k_reset, k_step (float32 obs), k_rollout, k_rollout2, k_mt_sync, k_render,
+//                       k_export, k_obs_f32, k_grayscale, k_grayscale_sweep, k_gen_actions, k_check_actions,
+//                       k_gate_actions, k_policy_greedy
+//   st_step_packed.hip  k_step (packed obs: the prologue-draw schedule)
+//   st_step_export.hip  k_step_export
+//   st_afterstates.hip  k_afterstates, k_placement_actions, k_place, k_play_sum, k_policy_linear
+//   st_features.hip     k_afterstates_set, k_policy_linear_set
+//   st_lookahead.hip    k_next_piece, k_policy_lookahead
+//   st_expect.hip       k_next_weights, k_policy_expect
+//   st_reachable.hip    k_reachable
+//   st_routes.hip       k_routes, k_route_pop
+//   st_locks.hip        k_lock_set, k_afterstates_at, k_locks
+//   st_fork.hip         k_fork
 #include "st_internal.h"
-
-#if defined(ST_STEP_EXPORT_TU) || defined(ST_STEP_PACKED_TU) || defined(ST_AFTERSTATES_TU) || defined(ST_REACHABLE_TU) || \
-    defined(ST_FEATURES_TU) || defined(ST_LOOKAHEAD_TU) || defined(ST_ROUTES_TU) || defined(ST_FORK_TU) ||              \
-    defined(ST_EXPECT_TU) || defined(ST_LOCKS_TU)
-#define ST_SIDE_TU 1  // not the library's own translation unit
-#endif
-#if defined(ST_AFTERSTATES_TU) || defined(ST_FEATURES_TU) || defined(ST_LOOKAHEAD_TU) || defined(ST_ROUTES_TU) || \
-    defined(ST_EXPECT_TU) || defined(ST_LOCKS_TU)
-#define ST_EVAL_TU 1  // the translation units that evaluate slots (eval_slot)
-#endif
-
 
 namespace st {
 namespace {
@@ -3396,7 +3386,122 @@ constexpr uint32_t kScoringFlags =
     ST_PENALISE_HEIGHT | ST_PENALISE_HEIGHT_INCREASE | ST_ADVANCED_CLEARS | ST_HIGH_SCORING |
     ST_PENALISE_HOLES | ST_PENALISE_HOLES_INCREASE;
 
+// ---------------------------------------------------------------- shared with side units
+// What the library's own kernels (below the switch) share with one side unit.
+//
+// mt_sync_lanes is the per-env part of k_mt_sync (below: every env back to
+// CPython's form), shared with k_fork (st_fork.hip), which puts exactly the
+// envs it writes under ST_FORK_KEEP_RNG into that form: lane's env e0 + lane
+// has the index word r; the lanes with `on` get their generation into buffer A
+// (wave-uniform: every lane of the wave calls it); returns CPython's index.
+__device__ __forceinline__ int mt_sync_lanes(uint32_t *mt, int64_t e0, uint32_t r, bool on, int lane) {
+    int idx = (int)(r & 0x3FFu);
+    uint32_t cur = (r >> 20) & 1u;
+    if (pv_ok(r)) {
+        // A preview draw always starts where an earlier draw ended (index
+        // >= 1 of its generation), so idx > c: it stayed in one generation;
+        // idx <= c: it started at index 624 - (c - idx) of the previous one,
+        // which is intact (nothing is built into it while the preview is
+        // pending).  idx == c is a draw that started exactly at 624: CPython
+        // holds the old words with index 624 (it twists lazily).
+        const int c = (int)((r >> 25) & kPvCMax);
+        if (idx > c) {
+            idx -= c;
+        } else {
+            idx = kMtN - (c - idx);
+            cur ^= 1u;
+        }
+    }
+    uint64_t inb = __ballot(on && cur);
+    while (inb) {
+        const int l = __builtin_ctzll(inb);
+        inb &= inb - 1;
+        uint32_t *g = mt + (e0 + l) * kMtPitch;
+        uint32_t t[10];
+#pragma unroll
+        for (int q = 0; q < 10; ++q) {
+            const int i = lane + kWave * q;
+            t[q] = i < kMtN ? g[kMtB + i] : 0u;
+        }
+#pragma unroll
+        for (int q = 0; q < 10; ++q) {
+            const int i = lane + kWave * q;
+            if (i < kMtN) g[i] = t[q];
+        }
+    }
+    return idx;
+}
+
+// export_record is shared by k_export (below) and k_step_export (st_step_export.hip).
+// st_export_env: one env's outputs and state as one record (the single-env
+// surface's per-step read-back in one transfer): obs words | reward | done |
+// stats rows | MT words (optional) | float32 obs (optional).  The MT index
+// row and words are CPython's form, computed read-only the way k_mt_sync
+// rewrites them (the preview's words given back, the generation holding that
+// position): the env keeps its preview and next-generation progress.  The
+// float32 obs saves the host the bit unpacking (the record is written
+// straight into mapped pinned memory).
+// One writer for both launches that produce it (k_export and k_step_export's
+// tail): thread `tid` of `nthreads` cooperating threads.  Its loads are
+// non-temporal (served by L2, past the CU's L1): in k_step_export they read
+// what other waves of the workgroup stored in the same launch.
+template <typename T>
+__device__ __forceinline__ T ld_l2(const T *p) {
+    return __builtin_nontemporal_load(p);
+}
+__device__ __forceinline__ void export_record(const KParams &p, int64_t env, const uint32_t *obs, const int32_t *rew,
+                                              const uint8_t *done, uint32_t parts, uint32_t *out, int tid,
+                                              int nthreads) {
+    const int W = p.W, H = p.H;
+    const int head = W + 2 + ST_NSTAT;
+    const uint32_t r = (uint32_t)ld_l2(&p.stats[(int64_t)ST_STAT_MT_INDEX * p.stride + env]);
+    int idx = (int)(r & 0x3FFu);
+    uint32_t cur = (r >> 20) & 1u;
+    if (pv_ok(r)) {  // see k_mt_sync
+        const int c = (int)((r >> 25) & kPvCMax);
+        if (idx > c) {
+            idx -= c;
+        } else {
+            idx = kMtN - (c - idx);
+            cur ^= 1u;
+        }
+    }
+    for (int i = tid; i < head; i += nthreads) {
+        uint32_t v;
+        if (i < W) v = obs ? ld_l2(&obs[(int64_t)i * p.n + env]) : 0u;
+        else if (i == W) v = rew ? (uint32_t)ld_l2(&rew[env]) : 0u;
+        else if (i == W + 1) v = done ? (uint32_t)ld_l2(&done[env]) : 0u;
+        else if (i == W + 2 + ST_STAT_MT_INDEX) v = (uint32_t)idx;
+        else v = (uint32_t)ld_l2(&p.stats[(int64_t)(i - W - 2) * p.stride + env]);
+        out[i] = v;
+    }
+    if (parts & ST_EXPORT_MT) {
+        const uint32_t *g = p.mt + env * kMtPitch + (cur ? kMtB : 0u);
+        for (int i = tid; i < kMtN; i += nthreads) out[head + i] = ld_l2(&g[i]);
+    }
+    if (parts & ST_EXPORT_OBS_F32) {
+        float *f = reinterpret_cast<float *>(out + head + kMtN);
+        for (int i = tid; i < W * H; i += nthreads) {
+            const int x = i / H, y = i - x * H;
+            const uint32_t w = obs ? ld_l2(&obs[(int64_t)x * p.n + env]) : 0u;
+            f[i] = (float)((w >> y) & 1u);
+        }
+    }
+}
+
+}  // namespace
+}  // namespace st
+
+// k_step's arguments: the preloaded six, then the whole KParams
+#define ST_STEP_ARGS(p) (p).board, (p).stats, (p).actions, (p).mt, (p).stride, (p).n, (p)
+
+// ================================================================ the library's own unit
+// Everything below is compiled in st_kernels.hip's own unit alone; a side unit
+// (ST_SIDE_TU) sees the text above and adds its own kernels and launchers.
 #ifndef ST_SIDE_TU
+namespace st {
+namespace {
+
 // ---------------------------------------------------------------- reset
 // TetrisEngine.clear (tetris_env.py:306-315) on masked envs.  n_deaths,
 // shape_counts and the lock-delay counter persist (R15).
@@ -3502,7 +3607,6 @@ __global__ void k_seed(KParams p) {
     for (int x = 0; x < p.W; ++x) p.board[x * sd + e] = 0u;
     p.piece[e] = pack_piece(0, 0, p.W / 2, 0, 0);
 }
-#endif  // !ST_SIDE_TU
 
 // ---------------------------------------------------------------- MT sync
 // st_mt_sync: every env back to CPython's form (see "Double-buffered twist"):
@@ -3514,49 +3618,7 @@ __global__ void k_seed(KParams p) {
 // generation's progress restarts at 0, the preview is dropped: the next spawn
 // draws its piece, then a new preview).  One wave per 64 envs; it copies its
 // lanes' B buffers one env at a time, cooperatively.
-// mt_sync_lanes is the per-env part, shared with k_fork (st_fork.hip), which puts exactly the
-// envs it writes under ST_FORK_KEEP_RNG into that form: lane's env e0 + lane
-// has the index word r; the lanes with `on` get their generation into buffer A
-// (wave-uniform: every lane of the wave calls it); returns CPython's index.
-__device__ __forceinline__ int mt_sync_lanes(uint32_t *mt, int64_t e0, uint32_t r, bool on, int lane) {
-    int idx = (int)(r & 0x3FFu);
-    uint32_t cur = (r >> 20) & 1u;
-    if (pv_ok(r)) {
-        // A preview draw always starts where an earlier draw ended (index
-        // >= 1 of its generation), so idx > c: it stayed in one generation;
-        // idx <= c: it started at index 624 - (c - idx) of the previous one,
-        // which is intact (nothing is built into it while the preview is
-        // pending).  idx == c is a draw that started exactly at 624: CPython
-        // holds the old words with index 624 (it twists lazily).
-        const int c = (int)((r >> 25) & kPvCMax);
-        if (idx > c) {
-            idx -= c;
-        } else {
-            idx = kMtN - (c - idx);
-            cur ^= 1u;
-        }
-    }
-    uint64_t inb = __ballot(on && cur);
-    while (inb) {
-        const int l = __builtin_ctzll(inb);
-        inb &= inb - 1;
-        uint32_t *g = mt + (e0 + l) * kMtPitch;
-        uint32_t t[10];
-#pragma unroll
-        for (int q = 0; q < 10; ++q) {
-            const int i = lane + kWave * q;
-            t[q] = i < kMtN ? g[kMtB + i] : 0u;
-        }
-#pragma unroll
-        for (int q = 0; q < 10; ++q) {
-            const int i = lane + kWave * q;
-            if (i < kMtN) g[i] = t[q];
-        }
-    }
-    return idx;
-}
-
-#ifndef ST_SIDE_TU
+// mt_sync_lanes (above the switch) is the per-env part.
 __global__ __launch_bounds__(kWave) void k_mt_sync(KParams p) {
     const int lane = threadIdx.x;
     const int64_t e0 = (int64_t)blockIdx.x * kWave;
@@ -3587,123 +3649,15 @@ __global__ __launch_bounds__(kWave) void k_render(KParams p) {
     if (e < p.n)
         for (int x = 0; x < W; ++x) p.obs[x * p.n + e] = lcol(L, x, lane) & hmask;
 }
-#endif  // !ST_SIDE_TU
 
 // ---------------------------------------------------------------- export
-// st_export_env: one env's outputs and state as one record (the single-env
-// surface's per-step read-back in one transfer): obs words | reward | done |
-// stats rows | MT words (optional) | float32 obs (optional).  The MT index
-// row and words are CPython's form, computed read-only the way k_mt_sync
-// rewrites them (the preview's words given back, the generation holding that
-// position): the env keeps its preview and next-generation progress.  The
-// float32 obs saves the host the bit unpacking (the record is written
-// straight into mapped pinned memory).
-// One writer for both launches that produce it (k_export and k_step_export's
-// tail): thread `tid` of `nthreads` cooperating threads.  Its loads are
-// non-temporal (served by L2, past the CU's L1): in k_step_export they read
-// what other waves of the workgroup stored in the same launch.
-template <typename T>
-__device__ __forceinline__ T ld_l2(const T *p) {
-    return __builtin_nontemporal_load(p);
-}
-__device__ __forceinline__ void export_record(const KParams &p, int64_t env, const uint32_t *obs, const int32_t *rew,
-                                              const uint8_t *done, uint32_t parts, uint32_t *out, int tid,
-                                              int nthreads) {
-    const int W = p.W, H = p.H;
-    const int head = W + 2 + ST_NSTAT;
-    const uint32_t r = (uint32_t)ld_l2(&p.stats[(int64_t)ST_STAT_MT_INDEX * p.stride + env]);
-    int idx = (int)(r & 0x3FFu);
-    uint32_t cur = (r >> 20) & 1u;
-    if (pv_ok(r)) {  // see k_mt_sync
-        const int c = (int)((r >> 25) & kPvCMax);
-        if (idx > c) {
-            idx -= c;
-        } else {
-            idx = kMtN - (c - idx);
-            cur ^= 1u;
-        }
-    }
-    for (int i = tid; i < head; i += nthreads) {
-        uint32_t v;
-        if (i < W) v = obs ? ld_l2(&obs[(int64_t)i * p.n + env]) : 0u;
-        else if (i == W) v = rew ? (uint32_t)ld_l2(&rew[env]) : 0u;
-        else if (i == W + 1) v = done ? (uint32_t)ld_l2(&done[env]) : 0u;
-        else if (i == W + 2 + ST_STAT_MT_INDEX) v = (uint32_t)idx;
-        else v = (uint32_t)ld_l2(&p.stats[(int64_t)(i - W - 2) * p.stride + env]);
-        out[i] = v;
-    }
-    if (parts & ST_EXPORT_MT) {
-        const uint32_t *g = p.mt + env * kMtPitch + (cur ? kMtB : 0u);
-        for (int i = tid; i < kMtN; i += nthreads) out[head + i] = ld_l2(&g[i]);
-    }
-    if (parts & ST_EXPORT_OBS_F32) {
-        float *f = reinterpret_cast<float *>(out + head + kMtN);
-        for (int i = tid; i < W * H; i += nthreads) {
-            const int x = i / H, y = i - x * H;
-            const uint32_t w = obs ? ld_l2(&obs[(int64_t)x * p.n + env]) : 0u;
-            f[i] = (float)((w >> y) & 1u);
-        }
-    }
-}
-
-#ifndef ST_SIDE_TU
+// st_export_env's own launch (export_record, above the switch)
 __global__ __launch_bounds__(256) void k_export(KParams p, int64_t env, const uint32_t *obs,
                                                const int32_t *rew, const uint8_t *done, uint32_t parts,
                                                uint32_t *out) {
     export_record(p, env, obs, rew, done, parts, out, (int)threadIdx.x, (int)blockDim.x);
 }
 
-#elif defined(ST_STEP_EXPORT_TU)
-// st_step_export: k_step (packed outputs, no stamps, not gated) with the
-// export record of one env written by the workgroup that stepped it -- the
-// single-env surface's step and read-back in ONE launch.  Both waves run
-// step_logic / step_draw_once unchanged and meet at one more workgroup barrier
-// (each has passed B0 once: neither role returns early without VEC);
-// behind it the workgroup's 128 threads write the record from what the two
-// waves stored to global memory moments before: obs / reward / done and the
-// hot counter rows (logic wave), the count rows, the MT index word, the MT
-// words and the next-generation chunk (draw wave).
-// What orders the tail's loads behind those stores ("The fused
-// tail"): (1) each wave waits for its own stores before it arrives -- an
-// explicit s_waitcnt vmcnt(0), because a workgroup-scope release fence on
-// gfx950 waits for LDS traffic only and s_barrier waits for no counter; a
-// store counted out of vmcnt has been acknowledged by L2, `nt` or not;
-// (2) the workgroup barrier; (3) the tail's loads are issued behind it (the
-// acquire fence keeps the compiler from moving them up), are vector loads
-// (memory the kernel itself stored to is never read through the scalar
-// cache) and non-temporal, i.e. served by L2, where the stores are.  Were
-// they served by the CU's L1 instead, the LLVM AMDGPU memory model's rule for
-// gfx942 / gfx950 would hold: the waves of a workgroup share one
-// write-through L1 (no threadgroup-split mode here), which their stores
-// went through.  Other workgroups skip the wait, the barrier and the tail
-// (the branch is workgroup-uniform): for them this is k_step.
-template <int WT, int HT, bool SC0>
-__global__ __launch_bounds__(2 * kWave) void k_step_export(uint32_t *board, int32_t *stats, const uint8_t *actions,
-                                                           uint32_t *mt, int64_t stride, int64_t n, KParams p0,
-                                                           int64_t env, uint32_t *obs, int32_t *rew, uint8_t *done,
-                                                           uint32_t parts, uint32_t *out) {
-    KParams p = p0;
-    p.board = board;
-    p.stats = stats;
-    p.actions = actions;
-    p.mt = mt;
-    p.stride = stride;
-    p.n = n;
-    p.obs = obs;
-    p.reward = rew;
-    p.done = done;
-    __shared__ StepLds<WT, false, 1> sm;
-    if (threadIdx.x < kWave) step_logic<WT, HT, false, false, 1, SC0, false>(p, sm);
-    else step_draw_once<WT, HT, false, false, SC0, false>(p, sm);
-    if ((int64_t)blockIdx.x != env / kWave) return;
-    __builtin_amdgcn_s_setprio(0);  // the tail is nobody's critical chain
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have reached L2
-    wg_barrier();
-    export_record(p, env, obs, rew, done, parts, out, (int)threadIdx.x, 2 * kWave);
-}
-#endif  // ST_STEP_EXPORT_TU
-
-#ifndef ST_SIDE_TU
 // ---------------------------------------------------------------- misc
 // Image writers: the output of a block of envs is one contiguous region, so
 // lanes walk it in 16-B chunks (lane-consecutive vector stores, one 1-KB
@@ -4163,2576 +4117,8 @@ __global__ __launch_bounds__(kWave) void k_policy_greedy(KParams p, uint64_t see
     if ((uint32_t)(h % 1000ull) < explore) a = (uint32_t)((h >> 32) % 7ull);
     if (e < p.n) out[e] = (uint8_t)a;
 }
-#endif  // !ST_SIDE_TU
-
-#ifdef ST_EVAL_TU
-// ---------------------------------------------------------------- afterstates
-// st_afterstates: what k_policy_greedy evaluates and throws away, as an
-// output.  For env e's board and current piece id, every placement slot
-// s = rot * (W + 6) + (x + 3) (k_policy_greedy's (rot, x) loop order): the
-// piece at (x, 0) in rotation rot is valid iff not is_occupied
-// (tetris_env.py:29-36), is hard-dropped (:54-59), set (_set_piece's
-// clipping, :323-327) and the full rows are cleared (:205-216); the rows of
-// st_after_feat and, optionally, the resulting board are written.  The
-// piece's present rot, anchor and lock counter play no part, nor does
-// lock_delay; no state is written.
-// One wave per env, lane = slot, ceil(S / 64) passes.  The env's W column
-// words are wave-uniform: lanes 0 .. W + 15 load one word each (floor bits,
-// all-ones walls, as k_policy_greedy stages them) into W + 16 LDS words, and
-// every later column read is a broadcast (all lanes one address) or, for the
-// four box columns, at most W + 16 distinct addresses.  Outputs have the slot
-// innermost, so each row leaves as one contiguous store per wave.
-// REWARD is lock_score's -- the rules of the step that locks the piece there
-// (:256-297) under the context's flags, from the env's holes and
-// piece_height counters.
-//
-// One slot's evaluation, shared by k_afterstates and k_policy_linear: the
-// collision test, the drop, the overlay, the clear, the column pass and
-// lock_score.  C: the wave's column words, column c at C[c] (c in [-P, W + P));
-// s: a slot in [0, S); f: the rows of st_after_feat as the slot has them if it
-// is valid (the caller masks the rows of an invalid one); col_out(c, w, valid):
-// column c of the board after the clear.  Returns the slot's validity.
-template <class ColOut>
-__device__ __forceinline__ bool eval_slot(const uint32_t *C, int W, int H, uint32_t flags, int id, int s,
-                                          int32_t old_holes, int32_t old_height, int32_t (&f)[ST_AFTER_NFEAT],
-                                          ColOut col_out) {
-    const uint32_t hmask = (1u << H) - 1u, floorb = ~hmask;
-    const int per = W + 6;
-    const int r = (s >= per) + (s >= 2 * per) + (s >= 3 * per), x = s - r * per - 3;
-    const uint32_t m = c_tab_m[id * 4 + r], g = c_tab_g[id * 4 + r];
-    const int x0 = box_x0(g, x);
-    uint32_t v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = C[x0 + j];
-    const bool valid = !collides_v(m, 0, v);
-    const int y = valid ? drop_box(g, 0, v) : 0;
-    bool above = false;
-    uint32_t pb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t byte = (m >> (8 * j)) & 0xFFu;
-        above = above || (byte != 0u && y + __builtin_ctz(byte) - 3 < 0);  // (a box column without cells)
-        pb[j] = pc_bits(m, j, y) & hmask;
-    }
-    // the board with the piece: column c gets the bits of the box column at c
-    uint32_t andv = hmask;
-    for (int c = 0; c < W; ++c) {
-        uint32_t w = C[c];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
-        andv &= w;
-    }
-    const int32_t ncl = __builtin_popcount(andv);
-    int32_t holes = 0, agg = 0, bump = 0, hprev = 0;
-    uint32_t orv = 0;
-    for (int c = 0; c < W; ++c) {
-        uint32_t w = C[c] & hmask;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
-        if (andv) w = compact(w, andv);
-        const int32_t h = H - (int32_t)__builtin_ctz(w | floorb);  // the column's height
-        holes += h - __builtin_popcount(w);
-        agg += h;
-        bump += c ? (h > hprev ? h - hprev : hprev - h) : 0;
-        hprev = h;
-        orv |= w;
-        col_out(c, w, valid);
-    }
-    int32_t rew = (flags & ST_REWARD_STEP) ? 1 : 0;  // :256
-    int32_t score = 0, lines = 0, nholes = 0, height = 0, deaths = 0;
-    lock_score<false>(flags, ncl, orv, [&] { return holes; }, old_holes, old_height, rew, score, lines, nholes, height,
-                      deaths);
-    f[ST_AFTER_VALID] = 1;
-    f[ST_AFTER_Y] = y;
-    f[ST_AFTER_LINES] = ncl;
-    f[ST_AFTER_HOLES] = holes;
-    f[ST_AFTER_HEIGHT] = orv ? H - (int32_t)__builtin_ctz(orv) : 0;
-    f[ST_AFTER_ROWS] = __builtin_popcount(orv);
-    f[ST_AFTER_ABOVE] = above ? 1 : 0;
-    f[ST_AFTER_DEAD] = (int32_t)(orv & 1u);
-    f[ST_AFTER_REWARD] = rew;
-    f[ST_AFTER_AGG_HEIGHT] = agg;
-    f[ST_AFTER_BUMPINESS] = bump;
-    return valid;
-}
-
-// eval_slot_set<SET>: eval_slot with the rows of a feature set, for the
-// kernels of st_features.hip.  It restates eval_slot (which stays word for word
-// what k_afterstates and k_policy_linear were compiled from: a set parameter
-// on eval_slot itself, every extension statement under if constexpr, moved
-// three instructions of theirs) and must follow it change for change; the
-// tests hold the base rows of both against the same oracle.
-// SET = ST_FEATS_BCTS adds the rows of st_after_ext (simpletetris.h, "Feature
-// sets") behind st_after_feat's, from what the walks hold anyway: LANDING2 and
-// ERODED from the piece's box bytes / box bits and the full-row mask, the
-// other five from the column words of the second walk -- a column's word,
-// its left neighbour's and the one before that (a well of column c - 1 is
-// known once column c is), walls as all-ones words of H bits.
-constexpr int feat_rows(int set) { return set == ST_FEATS_BCTS ? ST_AFTER_NFEAT + ST_AFTER_NEXT : ST_AFTER_NFEAT; }
-
-// sum of d (d + 1) / 2 over the runs of set bits of m, d a run's length
-__device__ __forceinline__ int32_t well_sum(uint32_t m) {
-    int32_t sum = 0;
-    while (m) {
-        sum += __builtin_popcount(m);
-        m &= m << 1;
-    }
-    return sum;
-}
-
-// the extension rows' state over the second walk: the two columns left of
-// c and the sums of the per-column rows (nothing in the base set)
-template <bool EXT>
-struct ExtAcc {};
-template <>
-struct ExtAcc<true> {
-    uint32_t w1, w2, hole_or = 0;
-    int32_t rtr = 0, ctr = 0, wells = 0, hdepth = 0;
-};
-
-template <int SET, class ColOut>
-__device__ __forceinline__ bool eval_slot_set(const uint32_t *C, int W, int H, uint32_t flags, int id, int s,
-                                              int32_t old_holes, int32_t old_height,
-                                              int32_t (&f)[feat_rows(SET)], ColOut col_out) {
-    constexpr bool EXT = SET == ST_FEATS_BCTS;
-    const uint32_t hmask = (1u << H) - 1u, floorb = ~hmask;
-    const int per = W + 6;
-    const int r = (s >= per) + (s >= 2 * per) + (s >= 3 * per), x = s - r * per - 3;
-    const uint32_t m = c_tab_m[id * 4 + r], g = c_tab_g[id * 4 + r];
-    const int x0 = box_x0(g, x);
-    uint32_t v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = C[x0 + j];
-    const bool valid = !collides_v(m, 0, v);
-    const int y = valid ? drop_box(g, 0, v) : 0;
-    bool above = false;
-    uint32_t pb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t byte = (m >> (8 * j)) & 0xFFu;
-        above = above || (byte != 0u && y + __builtin_ctz(byte) - 3 < 0);  // (a box column without cells)
-        pb[j] = pc_bits(m, j, y) & hmask;
-    }
-    // the board with the piece: column c gets the bits of the box column at c
-    uint32_t andv = hmask;
-    for (int c = 0; c < W; ++c) {
-        uint32_t w = C[c];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
-        andv &= w;
-    }
-    const int32_t ncl = __builtin_popcount(andv);
-    int32_t holes = 0, agg = 0, bump = 0, hprev = 0;
-    uint32_t orv = 0;
-    ExtAcc<EXT> x_;
-    if constexpr (EXT) x_.w1 = x_.w2 = hmask;  // the left wall
-    for (int c = 0; c < W; ++c) {
-        uint32_t w = C[c] & hmask;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
-        if (andv) w = compact(w, andv);
-        if constexpr (EXT) {
-            x_.rtr += __builtin_popcount(x_.w1 ^ w);
-            const uint32_t wf = w | (1u << H);  // the floor counts as filled
-            x_.ctr += __builtin_popcount((wf ^ (wf >> 1)) & hmask);
-            if (c) x_.wells += well_sum(~x_.w1 & x_.w2 & w & hmask);  // column c - 1
-            const uint32_t top = w & (0u - w);                // the column's topmost cell (0: none)
-            uint32_t hl = ~w & hmask & ~(top | (top - 1u));   // its holes: empty, below the top
-            x_.hole_or |= hl;
-            while (hl) {
-                x_.hdepth += __builtin_popcount(w & ((hl & (0u - hl)) - 1u));  // the cells above this hole
-                hl &= hl - 1u;
-            }
-            x_.w2 = x_.w1;
-            x_.w1 = w;
-        }
-        const int32_t h = H - (int32_t)__builtin_ctz(w | floorb);  // the column's height
-        holes += h - __builtin_popcount(w);
-        agg += h;
-        bump += c ? (h > hprev ? h - hprev : hprev - h) : 0;
-        hprev = h;
-        orv |= w;
-        col_out(c, w, valid);
-    }
-    int32_t rew = (flags & ST_REWARD_STEP) ? 1 : 0;  // :256
-    int32_t score = 0, lines = 0, nholes = 0, height = 0, deaths = 0;
-    lock_score<false>(flags, ncl, orv, [&] { return holes; }, old_holes, old_height, rew, score, lines, nholes, height,
-                      deaths);
-    f[ST_AFTER_VALID] = 1;
-    f[ST_AFTER_Y] = y;
-    f[ST_AFTER_LINES] = ncl;
-    f[ST_AFTER_HOLES] = holes;
-    f[ST_AFTER_HEIGHT] = orv ? H - (int32_t)__builtin_ctz(orv) : 0;
-    f[ST_AFTER_ROWS] = __builtin_popcount(orv);
-    f[ST_AFTER_ABOVE] = above ? 1 : 0;
-    f[ST_AFTER_DEAD] = (int32_t)(orv & 1u);
-    f[ST_AFTER_REWARD] = rew;
-    f[ST_AFTER_AGG_HEIGHT] = agg;
-    f[ST_AFTER_BUMPINESS] = bump;
-    if constexpr (EXT) {
-        x_.rtr += __builtin_popcount(x_.w1 ^ hmask);    // the last column against the right wall
-        x_.wells += well_sum(~x_.w1 & x_.w2 & hmask);   // column W - 1 (W >= 4: w2 is column W - 2)
-        // the rows the piece spans, unclipped: bit dy + 3 of a box byte is row y + dy
-        const uint32_t span = (m | m >> 8 | m >> 16 | m >> 24) & 0xFFu;
-        const int32_t ymin = y + (int32_t)__builtin_ctz(span) - 3, ymax = y + 28 - (int32_t)__builtin_clz(span);
-        int32_t gone = 0;  // cells of the piece, inside the board, in a row that was cleared
-#pragma unroll
-        for (int j = 0; j < 4; ++j) gone += __builtin_popcount(pb[j] & andv);
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_LANDING2] = 2 * H - 1 - (ymin + ymax);
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_ERODED] = ncl * gone;
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_ROW_TRANS] = x_.rtr;
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_COL_TRANS] = x_.ctr;
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_WELLS] = x_.wells;
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_HOLE_DEPTH] = x_.hdepth;
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_HOLE_ROWS] = __builtin_popcount(x_.hole_or);
-    }
-    return valid;
-}
-#endif  // ST_EVAL_TU
-
-#if defined(ST_EVAL_TU) || defined(ST_REACHABLE_TU)
-// The wave's W + 2 * P column words (floor bits, all-ones walls): lanes
-// 0 .. W + 2 * P - 1 write one word each.
-constexpr int kAfterP = 8;  // wall columns each side: the box's columns span [-6, W + 5]
-constexpr int kAfterCols = kMaxW + 2 * kAfterP;
-__device__ __forceinline__ void stage_env_columns(uint32_t *L, const KParams &p, int64_t e, int lane) {
-    if (lane < p.W + 2 * kAfterP) {
-        const int c = lane - kAfterP;
-        L[lane] = c >= 0 && c < p.W ? p.board[c * p.stride + e] | ~((1u << p.H) - 1u) : ~0u;
-    }
-}
-#endif
-
-#ifdef ST_EVAL_TU
-
-#ifdef ST_AFTERSTATES_TU
-__global__ __launch_bounds__(kWave) void k_afterstates(KParams p, int32_t *__restrict__ feat,
-                                                       uint32_t *__restrict__ boards) {
-    __shared__ uint32_t L[kAfterCols];
-    const int lane = threadIdx.x;
-    const int64_t e = blockIdx.x;  // the grid is p.n waves: padding envs are not evaluated
-    const int64_t sd = p.stride;
-    const int W = p.W, H = p.H;
-    const int S = 4 * (W + 6);
-    stage_env_columns(L, p, e, lane);
-    const uint32_t pid = p.piece[e] & 7u;
-    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
-    const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
-    const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd + e];
-    wave_sync();
-    const size_t fbase = (size_t)e * ST_AFTER_NFEAT * S, bbase = (size_t)e * W * S;
-    for (int s0 = 0; s0 < S; s0 += kWave) {
-        const int s = s0 + lane;
-        const bool live = s < S;
-        const int sc = live ? s : S - 1;  // (lanes past the last slot compute it again, store nothing)
-        int32_t f[ST_AFTER_NFEAT];
-        const bool valid = eval_slot(L + kAfterP, W, H, p.flags, id, sc, old_holes, old_height, f,
-                                     [&](int c, uint32_t w, bool ok) {
-                                         if (boards && live) boards[bbase + (size_t)c * S + s] = ok ? w : 0u;
-                                     });
-        if (live) {
-#pragma unroll
-            for (int row = 0; row < ST_AFTER_NFEAT; ++row) feat[fbase + (size_t)row * S + s] = valid ? f[row] : 0;
-        }
-    }
-}
-#else
-// k_afterstates with the rows of SET: feat [n][feat_rows(SET)][S]
-template <int SET>
-__global__ __launch_bounds__(kWave) void k_afterstates_set(KParams p, int32_t *__restrict__ feat,
-                                                           uint32_t *__restrict__ boards) {
-    constexpr int NF = feat_rows(SET);
-    __shared__ uint32_t L[kAfterCols];
-    const int lane = threadIdx.x;
-    const int64_t e = blockIdx.x;  // the grid is p.n waves: padding envs are not evaluated
-    const int64_t sd = p.stride;
-    const int W = p.W, H = p.H;
-    const int S = 4 * (W + 6);
-    stage_env_columns(L, p, e, lane);
-    const uint32_t pid = p.piece[e] & 7u;
-    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
-    const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
-    const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd + e];
-    wave_sync();
-    const size_t fbase = (size_t)e * NF * S, bbase = (size_t)e * W * S;
-    for (int s0 = 0; s0 < S; s0 += kWave) {
-        const int s = s0 + lane;
-        const bool live = s < S;
-        const int sc = live ? s : S - 1;  // (lanes past the last slot compute it again, store nothing)
-        int32_t f[NF];
-        const bool valid = eval_slot_set<SET>(L + kAfterP, W, H, p.flags, id, sc, old_holes, old_height, f,
-                                          [&](int c, uint32_t w, bool ok) {
-                                              if (boards && live) boards[bbase + (size_t)c * S + s] = ok ? w : 0u;
-                                          });
-        if (live) {
-#pragma unroll
-            for (int row = 0; row < NF; ++row) feat[fbase + (size_t)row * S + s] = valid ? f[row] : 0;
-        }
-    }
-}
-#endif
-
-#ifdef ST_AFTERSTATES_TU
-// st_placement_actions: the primitive action that moves env e's live piece
-// toward slot slots[e] -- k_policy_greedy's rule (gen_golden.greedy_action):
-// rotate_left until the rotation matches, then move toward x, then hard-drop;
-// a slot outside [0, S) hard-drops.  One lane per env.
-__global__ __launch_bounds__(256) void k_placement_actions(KParams p, const int32_t *__restrict__ slots,
-                                                           uint8_t *__restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.n) return;
-    const int per = p.W + 6;
-    const uint32_t pw = p.piece[e];
-    const int rot = (int)((pw >> 3) & 3u), ax = (int)((pw >> 5) & 63u);
-    const int32_t s = slots[e];
-    uint32_t a = 2u;
-    if (s >= 0 && s < 4 * per) {
-        const int trot = s / per, tx = s - trot * per - 3;
-        a = rot != trot ? 4u : (ax < tx ? 1u : (ax > tx ? 0u : 2u));
-    }
-    out[e] = (uint8_t)a;
-}
-#endif  // ST_AFTERSTATES_TU
-
-// ---------------------------------------------------------------- placement step
-// st_place: commit slot slots[e] of env e (simpletetris.h, "Placement step").
-// A VALID slot -- in [0, S) and not is_occupied(cells, (x, 0), board), the
-// validity of eval_slot on the env's current board and piece id -- makes the
-// env's piece the slot's: rotation rot, anchor (x, 0) and a lock counter of
-// lock_mod - 1 = max(lock_delay, 0), from which the next drop's
-// (x + 1) % lock_mod is 0 (tetris_env.py:175): the hard drop behind it locks
-// the piece whatever lock_delay is.  Any other slot leaves the piece word as
-// it is, lock counter included.  Board, counters, MT and preview are not
-// written.  Every shape holds cell (0, 0), so a valid slot has 0 <= x < W and
-// x fits its six bits.
-__device__ __forceinline__ uint32_t placed_piece(int id, int rot, int x, int lock_mod) {
-    return (uint32_t)id | (uint32_t)rot << 3 | (uint32_t)x << 5 | (uint32_t)(lock_mod - 1) << 17;  // anchor row 0
-}
-
-#ifdef ST_AFTERSTATES_TU
-// One lane per env: the piece word, the slot and the slot's four box columns
-// (floor bits, all-ones walls outside [0, W), as stage_env_columns gives them)
-// are the lane's only loads; the piece word leaves with a plain vector store.
-__global__ __launch_bounds__(256) void k_place(KParams p, const int32_t *__restrict__ slots,
-                                               uint8_t *__restrict__ placed) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.n) return;
-    const int W = p.W, per = W + 6;
-    const uint32_t pid = p.piece[e] & 7u;
-    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
-    const int32_t s = slots[e];
-    bool ok = false;
-    if (s >= 0 && s < 4 * per) {
-        const int r = (s >= per) + (s >= 2 * per) + (s >= 3 * per), x = s - r * per - 3;
-        const uint32_t m = c_tab_m[id * 4 + r], g = c_tab_g[id * 4 + r];
-        const int x0 = box_x0(g, x);  // in [-6, W + 2]
-        const uint32_t floorb = ~((1u << p.H) - 1u);
-        uint32_t v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int c = x0 + j;
-            v[j] = c >= 0 && c < W ? p.board[c * p.stride + e] | floorb : ~0u;
-        }
-        ok = !collides_v(m, 0, v);
-        if (ok) p.piece[e] = placed_piece(id, r, x, p.lock_mod);
-    }
-    if (placed) placed[e] = ok ? 1 : 0;
-}
-#endif  // ST_AFTERSTATES_TU
-
-// ---------------------------------------------------------------- linear feature player
-// st_policy_linear: env e scores every slot of its current piece with weight
-// row e % n_w and keeps the best one -- k_afterstates's evaluation (eval_slot)
-// without its output stream: per env 4 + 1 + 4 + 44 bytes leave the kernel.
-//
-// score = the float32 chain acc = acc + w[r] * (float)feat[r] over the rows
-// of st_after_feat in enum order from acc = 0, every product and every sum
-// rounded on its own.  No compiler flag can fuse the chain: lin_score passes
-// every product through an empty asm statement before it is added, so the
-// multiply and the add never meet in one expression the backend could
-// contract (-ffp-contract=fast on the command line included, which overrides
-// a `#pragma clang fp contract(off)`; __fmul_rn / __fadd_rn are plain * and +
-// in this toolchain's headers and would contract too).  The statement emits
-// no instruction.
-//
-// One wave per env, lane = slot, ceil(S / 64) passes; ST_POLICY_WAVES envs per
-// workgroup, each wave with its own W + 16 column words of LDS and no
-// workgroup barrier (a wave past the last env leaves at once).  A lane keeps
-// the first maximum of its own slots: the first pass sets it (10x20 has no
-// other), a later pass replaces it only on a strictly larger score, since a
-// lane's slots ascend.  Across lanes: the wave's maximum score over the lanes
-// that hold a candidate, then the lowest slot among the lanes that reach it --
-// two DPP reductions (wave_reduce), six VALU operations each, no LDS.  The lane
-// whose candidate won -- lane 0 if no slot is valid -- writes the env's
-// outputs with plain stores.
-//
-// st_play_linear's accumulators stay out of this kernel: its steps write
-// their reward / done into rows of a ring the context owns, and k_play_sum adds
-// a ring's worth at a time -- one lane per env, whole cache lines.  (Adding
-// in this kernel, one lane per wave or one wave per 64 envs, measured 3.8 /
-// 1.5 us per step at 65,536 envs.)
-#ifdef ST_AFTERSTATES_TU
-__global__ __launch_bounds__(256) void k_play_sum(const int32_t *__restrict__ reward, const uint8_t *__restrict__ done,
-                                                  int rows, int64_t n, int64_t *__restrict__ ret,
-                                                  int32_t *__restrict__ episodes, int32_t *__restrict__ out_reward,
-                                                  uint8_t *__restrict__ out_done) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    int64_t r = 0;
-    int32_t d = 0;
-    for (int j = 0; j < rows; ++j) {
-        r += (int64_t)reward[(int64_t)j * n + e];
-        d += done[(int64_t)j * n + e] ? 1 : 0;
-    }
-    if (ret) ret[e] += r;
-    if (episodes) episodes[e] += d;
-    // the last row, i.e. the last step's outputs, for the caller
-    if (out_reward) out_reward[e] = reward[(int64_t)(rows - 1) * n + e];
-    if (out_done) out_done[e] = done[(int64_t)(rows - 1) * n + e];
-}
-#endif  // ST_AFTERSTATES_TU
-
-template <int NF>
-__device__ __forceinline__ float lin_score(const float (&w)[NF], const int32_t (&f)[NF]) {
-#pragma clang fp contract(off)
-    float acc = 0.0f;
-#pragma unroll
-    for (int r = 0; r < NF; ++r) {
-        float prod = w[r] * (float)f[r];
-        asm volatile("" : "+v"(prod));  // the rounded product, opaque to the add below
-        acc = acc + prod;
-    }
-    return acc;
-}
-
-// op over the 64 lanes of a wave whose lanes are all active, in every lane:
-// within each row of 16 by quad permutes and row rotations, then row_bcast:15
-// into rows 1 and 3 and row_bcast:31 into rows 2 and 3 (gfx9 DPP), which leaves
-// the result in lane 63.  A lane the controls do not write keeps its own value
-// (old = x), and op(x, x) = x for the max / min this is used with.
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ int dpp_from(int x) {
-    return __builtin_amdgcn_update_dpp(x, x, CTRL, ROW_MASK, 0xF, false);
-}
-template <class Op>
-__device__ __forceinline__ int wave_reduce(int x, Op op) {
-    x = op(x, dpp_from<0xB1>(x));         // quad_perm:[1,0,3,2]
-    x = op(x, dpp_from<0x4E>(x));         // quad_perm:[2,3,0,1]
-    x = op(x, dpp_from<0x124>(x));        // row_ror:4
-    x = op(x, dpp_from<0x128>(x));        // row_ror:8
-    x = op(x, dpp_from<0x142, 0xA>(x));   // row_bcast:15 into rows 1, 3
-    x = op(x, dpp_from<0x143, 0xC>(x));   // row_bcast:31 into rows 2, 3
-    return __builtin_amdgcn_readlane(x, kWave - 1);
-}
-
-template <bool FIRST>
-struct PassTag {
-    static constexpr bool value = FIRST;
-};
-
-#ifndef ST_POLICY_WAVES
-#define ST_POLICY_WAVES 4  // envs (waves) per workgroup: the block-shape A/B, DESIGN "Linear feature player"
-#endif
-
-// COMMIT (st_play_linear_placements): the lane that writes the env's outputs
-// also stores the chosen slot's piece word (placed_piece: k_place's commit,
-// without its launch); it stores nothing if no slot is valid.
-#ifdef ST_AFTERSTATES_TU
-template <int WAVES, bool COMMIT = false>
-__global__ __launch_bounds__(WAVES *kWave) void k_policy_linear(KParams p, const float *__restrict__ wts, int64_t n_w,
-                                                                int32_t *__restrict__ slots,
-                                                                uint8_t *__restrict__ actions,
-                                                                float *__restrict__ scores,
-                                                                int32_t *__restrict__ best) {
-    __shared__ uint32_t Lall[WAVES * kAfterCols];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t e = (int64_t)blockIdx.x * WAVES + wave;
-    if (e >= p.n) return;  // (wave-uniform; the kernel has no workgroup barrier)
-    uint32_t *L = Lall + wave * kAfterCols;
-    const int64_t sd = p.stride;
-    const int W = p.W, H = p.H;
-    const int per = W + 6, S = 4 * per;
-    stage_env_columns(L, p, e, lane);
-    const uint32_t pw = p.piece[e];
-    const uint32_t pid = pw & 7u;
-    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
-    const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
-    const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd + e];
-    // e < 2^24 (st_create), so the row index is 32-bit arithmetic
-    const uint32_t wrow = n_w > e ? (uint32_t)e : (uint32_t)e % (uint32_t)n_w;
-    float w[ST_AFTER_NFEAT];
-#pragma unroll
-    for (int r = 0; r < ST_AFTER_NFEAT; ++r) w[r] = wts[(size_t)wrow * ST_AFTER_NFEAT + r];
-    wave_sync();
-    // the lane's candidate: its best slot so far (-1: none), that slot's score and rows
-    int32_t bslot;
-    float bscore;
-    int32_t bf[ST_AFTER_NFEAT];
-    auto pass = [&](int s0, auto first) {
-        const int s = s0 + lane;
-        const bool live = s < S;
-        int32_t f[ST_AFTER_NFEAT];
-        const bool valid = eval_slot(L + kAfterP, W, H, p.flags, id, live ? s : S - 1, old_holes, old_height, f,
-                                     [](int, uint32_t, bool) {});
-        const float sc = lin_score(w, f);
-        if constexpr (decltype(first)::value) {  // (score and rows are read only where bslot >= 0)
-            bslot = live && valid ? s : -1;
-            bscore = sc;
-#pragma unroll
-            for (int r = 0; r < ST_AFTER_NFEAT; ++r) bf[r] = f[r];
-        } else if (live && valid && (bslot < 0 || sc > bscore)) {
-            bslot = s;
-            bscore = sc;
-#pragma unroll
-            for (int r = 0; r < ST_AFTER_NFEAT; ++r) bf[r] = f[r];
-        }
-    };
-    pass(0, PassTag<true>{});
-    for (int s0 = kWave; s0 < S; s0 += kWave) pass(s0, PassTag<false>{});
-    // the wave's maximum over the candidates, then the lowest slot that reaches
-    // it.  With finite weights some candidate equals the maximum; a NaN score
-    // equals nothing, and then every candidate counts as reaching it, so that
-    // the slot stays a valid one.
-    const bool has = bslot >= 0;
-    const float top = __int_as_float(wave_reduce(__float_as_int(has ? bscore : -__builtin_inff()), [](int a, int b) {
-        return __float_as_int(__builtin_fmaxf(__int_as_float(a), __int_as_float(b)));
-    }));
-    bool tied = has && bscore == top;
-    if (__ballot(tied) == 0) tied = has;
-    const int32_t win = wave_reduce(tied ? bslot : INT32_MAX, [](int a, int b) { return a < b ? a : b; });
-    const bool none = win == INT32_MAX;  // no valid slot: lane 0 writes slot -1, action 2, score 0, zero rows
-    if (none ? lane == 0 : tied && bslot == win) {
-        if (slots) slots[e] = none ? -1 : win;
-        if (scores) scores[e] = none ? 0.0f : bscore;
-        if (actions) {
-            const int rot = (int)((pw >> 3) & 3u), ax = (int)((pw >> 5) & 63u);
-            const int trot = (win >= per) + (win >= 2 * per) + (win >= 3 * per), tx = win - trot * per - 3;
-            // k_placement_actions's rule
-            actions[e] = (uint8_t)(none ? 2u : rot != trot ? 4u : (ax < tx ? 1u : (ax > tx ? 0u : 2u)));
-        }
-        if (best) {
-#pragma unroll
-            for (int r = 0; r < ST_AFTER_NFEAT; ++r) best[(size_t)r * p.n + e] = none ? 0 : bf[r];
-        }
-        if constexpr (COMMIT) {
-            if (!none) {
-                const int trot = (win >= per) + (win >= 2 * per) + (win >= 3 * per), tx = win - trot * per - 3;
-                p.piece[e] = placed_piece(id, trot, tx, p.lock_mod);
-            }
-        }
-    }
-}
-#else
-// k_policy_linear over the rows of SET (weights [n_w][NF], best [NF][n]) and
-// with a slot mask: allowed int32 [n][S] or null; a slot is a candidate iff it
-// is valid and its word is not 0.
-template <int WAVES, bool COMMIT, int SET>
-__global__ __launch_bounds__(WAVES *kWave) void k_policy_linear_set(KParams p, const float *__restrict__ wts,
-                                                                    int64_t n_w, const int32_t *__restrict__ allowed,
-                                                                    int32_t *__restrict__ slots,
-                                                                    uint8_t *__restrict__ actions,
-                                                                    float *__restrict__ scores,
-                                                                    int32_t *__restrict__ best) {
-    __shared__ uint32_t Lall[WAVES * kAfterCols];
-    constexpr int NF = feat_rows(SET);
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t e = (int64_t)blockIdx.x * WAVES + wave;
-    if (e >= p.n) return;  // (wave-uniform; the kernel has no workgroup barrier)
-    uint32_t *L = Lall + wave * kAfterCols;
-    const int64_t sd = p.stride;
-    const int W = p.W, H = p.H;
-    const int per = W + 6, S = 4 * per;
-    stage_env_columns(L, p, e, lane);
-    const uint32_t pw = p.piece[e];
-    const uint32_t pid = pw & 7u;
-    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
-    const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
-    const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd + e];
-    // e < 2^24 (st_create), so the row index is 32-bit arithmetic
-    const uint32_t wrow = n_w > e ? (uint32_t)e : (uint32_t)e % (uint32_t)n_w;
-    float w[NF];
-#pragma unroll
-    for (int r = 0; r < NF; ++r) w[r] = wts[(size_t)wrow * NF + r];
-    wave_sync();
-    // the lane's candidate: its best slot so far (-1: none), that slot's score and rows
-    int32_t bslot;
-    float bscore;
-    int32_t bf[NF];
-    auto pass = [&](int s0, auto first) {
-        const int s = s0 + lane;
-        const bool live = s < S;
-        int32_t f[NF];
-        bool valid = eval_slot_set<SET>(L + kAfterP, W, H, p.flags, id, live ? s : S - 1, old_holes, old_height, f,
-                                    [](int, uint32_t, bool) {});
-        // (a slot the mask refuses is no candidate: from here on, as if invalid)
-        if (allowed) valid = valid && live && allowed[(size_t)e * S + s] != 0;
-        const float sc = lin_score(w, f);
-        if constexpr (decltype(first)::value) {  // (score and rows are read only where bslot >= 0)
-            bslot = live && valid ? s : -1;
-            bscore = sc;
-#pragma unroll
-            for (int r = 0; r < NF; ++r) bf[r] = f[r];
-        } else if (live && valid && (bslot < 0 || sc > bscore)) {
-            bslot = s;
-            bscore = sc;
-#pragma unroll
-            for (int r = 0; r < NF; ++r) bf[r] = f[r];
-        }
-    };
-    pass(0, PassTag<true>{});
-    for (int s0 = kWave; s0 < S; s0 += kWave) pass(s0, PassTag<false>{});
-    // the wave's maximum over the candidates, then the lowest slot that reaches
-    // it.  With finite weights some candidate equals the maximum; a NaN score
-    // equals nothing, and then every candidate counts as reaching it, so that
-    // the slot stays a valid one.
-    const bool has = bslot >= 0;
-    const float top = __int_as_float(wave_reduce(__float_as_int(has ? bscore : -__builtin_inff()), [](int a, int b) {
-        return __float_as_int(__builtin_fmaxf(__int_as_float(a), __int_as_float(b)));
-    }));
-    bool tied = has && bscore == top;
-    if (__ballot(tied) == 0) tied = has;
-    const int32_t win = wave_reduce(tied ? bslot : INT32_MAX, [](int a, int b) { return a < b ? a : b; });
-    const bool none = win == INT32_MAX;  // no valid slot: lane 0 writes slot -1, action 2, score 0, zero rows
-    if (none ? lane == 0 : tied && bslot == win) {
-        if (slots) slots[e] = none ? -1 : win;
-        if (scores) scores[e] = none ? 0.0f : bscore;
-        if (actions) {
-            const int rot = (int)((pw >> 3) & 3u), ax = (int)((pw >> 5) & 63u);
-            const int trot = (win >= per) + (win >= 2 * per) + (win >= 3 * per), tx = win - trot * per - 3;
-            // k_placement_actions's rule
-            actions[e] = (uint8_t)(none ? 2u : rot != trot ? 4u : (ax < tx ? 1u : (ax > tx ? 0u : 2u)));
-        }
-        if (best) {
-#pragma unroll
-            for (int r = 0; r < NF; ++r) best[(size_t)r * p.n + e] = none ? 0 : bf[r];
-        }
-        if constexpr (COMMIT) {
-            if (!none) {
-                const int trot = (win >= per) + (win >= 2 * per) + (win >= 3 * per), tx = win - trot * per - 3;
-                p.piece[e] = placed_piece(id, trot, tx, p.lock_mod);
-            }
-        }
-    }
-}
-#endif
-#endif  // ST_EVAL_TU
-
-#if defined(ST_LOOKAHEAD_TU) || defined(ST_EXPECT_TU)
-// the two-ply kernels' shape (k_policy_lookahead, k_policy_expect): one first-ply
-// slot per thread, the afterstate boards B1[s1][] in LDS at an odd row pitch
-constexpr int kLaWaves = 4;
-constexpr int kLaSlots = 4 * (kMaxW + 6);
-static_assert(kLaSlots <= kLaWaves * kWave, "one first-ply slot per thread");
-__host__ __device__ constexpr int la_pitch(int W) { return (W + 2 * kAfterP) | 1; }
-#endif
-
-#ifdef ST_LOOKAHEAD_TU
-// ---------------------------------------------------------------- next piece, two-ply player
-// st_next_piece: the shape _choose_shape (tetris_env.py:183-191) would return
-// for env e in its present state -- the piece its next _new_piece takes,
-// behind a lock or a reset: shape_counts changes only at a spawn and clear()
-// keeps it.  That is the preview (pv_id) where the MT word holds a valid one;
-// an env without one (a lock of st_step's, a host-written or synced state)
-// draws it here as st_step's prologue would -- k_reset's first draw: the counts
-// of the moment, not counted -- and keeps it (pv_pack), so the next spawn does
-// not draw again and st_mt_sync gives the words back.  One wave per 64 envs;
-// next: uint8 [n] or null (the draw alone).
-__global__ __launch_bounds__(kWave) void k_next_piece(KParams p, uint8_t *__restrict__ next) {
-    __shared__ uint32_t S[kMtN];
-    const int lane = threadIdx.x;
-    const int64_t e0 = (int64_t)blockIdx.x * kWave;
-    const int64_t e = e0 + lane;
-    const int64_t sd = p.stride;
-    const bool real = e < p.n;
-    int32_t *st = p.stats + e;  // (e < stride: the grid is stride / 64 waves)
-    int32_t cnt[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) cnt[i] = st[(ST_STAT_COUNT0 + i) * sd];
-    uint32_t mtst = (uint32_t)st[ST_STAT_MT_INDEX * sd];
-    const uint32_t mt0 = mtst;
-    int sid = pv_id(mt0);
-    const bool need = real && !pv_ok(mt0);
-    if (__ballot(need)) {
-        const MtPre nopre{};
-        const int pk = draw_shape<8, false>(need, cnt, mtst, p.mt + e0 * kMtPitch, S, lane, nopre, false);
-        if (need) {
-            sid = pk;
-            st[ST_STAT_MT_INDEX * sd] = (int32_t)pv_pack(mtst, pk, mt_consumed(mt0, mtst));
-        }
-    }
-    if (next && real) next[e] = (uint8_t)sid;
-}
-
-// st_policy_lookahead: the two-ply linear player (simpletetris.h, "Two-ply
-// player").  One workgroup of kLaWaves waves per env.
-//  1. stage: the env's column words (stage_env_columns), the piece, the
-//     counters and the preview (k_next_piece ran before this kernel on the
-//     stream: launch_policy_lookahead enqueues it).
-//  2. first ply: thread t evaluates slot s1 = t (S <= 152 < 256: one pass over
-//     the workgroup, waves past S idle) with eval_slot_set, whose col_out
-//     writes the afterstate's columns into B1[s1][] -- W + 2 * kAfterP words,
-//     floor bits, all-ones walls: the layout the evaluator reads -- at a row
-//     pitch of (W + 16) | 1 words (odd: the lanes of a wave, one row each,
-//     write one column to distinct banks).  It keeps S1, the candidate and dead
-//     flags and X(s1)'s holes / piece_height: lock_score's outputs on the
-//     slot's rows.
-//  3. live list: each wave's ballot of (candidate, not dead) in LDS; barrier.
-//  4. second ply: the waves walk the ballots in slot order and take the live
-//     s1 round-robin (the k-th live slot goes to wave k % kLaWaves); lane = s2,
-//     ceil(S / 64) passes of eval_slot_set on B1[s1] (broadcast reads) with the
-//     next piece and X(s1)'s counters, lin_score with the second weight row,
-//     k_policy_linear_set's two wave_reduces: M2 and its lowest s2 to LDS.
-//  5. choose: after a barrier thread t adds T to S1 (one float32 add), writes
-//     its table entries, and each wave reduces over its s1 the same way; after
-//     a last barrier thread 0 takes the first wave with the largest score and
-//     writes the env's outputs and, under COMMIT, the piece word (placed_piece).
-template <int SET, bool COMMIT>
-__global__ __launch_bounds__(kLaWaves *kWave) void k_policy_lookahead(
-    KParams p, const float *__restrict__ wts1, const float *__restrict__ wts2, int64_t n_w, float dead_value,
-    const int32_t *__restrict__ allowed, int32_t *__restrict__ slots, int32_t *__restrict__ slots2,
-    uint8_t *__restrict__ actions, float *__restrict__ scores, float *__restrict__ scores_all,
-    int32_t *__restrict__ slots2_all) {
-    constexpr int NF = feat_rows(SET);
-    // the output pointers wait in vector registers for the last phase: held as
-    // scalars across both plies they pushed the kernel past the SGPR file
-    asm volatile("" : "+v"(slots), "+v"(slots2), "+v"(actions), "+v"(scores), "+v"(scores_all), "+v"(slots2_all));
-    extern __shared__ uint32_t B1[];  // [S][la_pitch(W)]
-    __shared__ uint32_t L[kAfterCols];
-    __shared__ int32_t sHoles[kLaSlots], sHeight[kLaSlots], sSl2[kLaSlots];
-    __shared__ float sM2[kLaSlots];
-    __shared__ uint32_t sLive[kLaWaves][2];
-    __shared__ float sTop[kLaWaves];
-    __shared__ int32_t sWin[kLaWaves], sWin2[kLaWaves];
-    const int t = threadIdx.x, lane = t & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int64_t e = blockIdx.x;  // the grid is p.n workgroups: padding envs are not evaluated
-    const int64_t sd = p.stride;
-    const int W = p.W, H = p.H;
-    const int per = W + 6, S = 4 * per, pitch = la_pitch(W);
-    const uint32_t floorb = ~((1u << H) - 1u);
-    stage_env_columns(L, p, e, t);
-    const uint32_t pw = p.piece[e];
-    const uint32_t pid = pw & 7u;
-    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
-    const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
-    const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd + e];
-    const int nraw = pv_id((uint32_t)p.stats[ST_STAT_MT_INDEX * sd + e]);
-    const int nid = nraw < 7 ? nraw : 6;
-    // e < 2^24 (st_create), so the row index is 32-bit arithmetic
-    const uint32_t wrow = n_w > e ? (uint32_t)e : (uint32_t)e % (uint32_t)n_w;
-    __syncthreads();
-
-    // ---- first ply: s1 = t ----
-    const bool active = wave * kWave < S;  // (wave-uniform)
-    bool cand = false, dead1 = false;
-    float s1score = 0.0f;
-    if (active) {
-        const bool live = t < S;
-        const int s1 = live ? t : S - 1;  // (threads past the last slot compute it again, store nothing)
-        uint32_t *row = B1 + s1 * pitch;
-        if (live) {
-#pragma unroll
-            for (int j = 0; j < kAfterP; ++j) row[j] = row[kAfterP + W + j] = ~0u;
-        }
-        int32_t f[NF];
-        uint32_t orv = 0;
-        const bool valid = eval_slot_set<SET>(L + kAfterP, W, H, p.flags, id, s1, old_holes, old_height, f,
-                                              [&](int c, uint32_t w, bool) {
-                                                  orv |= w;
-                                                  if (live) row[kAfterP + c] = w | floorb;
-                                              });
-        cand = live && valid && (!allowed || allowed[(size_t)e * S + s1] != 0);
-        // the counters the lock of s1 leaves (:283-297): lock_score's, on the slot's rows
-        int32_t rew = 0, score = 0, lines = 0, holes1 = old_holes, height1 = old_height, deaths = 0;
-        const int32_t fholes = f[ST_AFTER_HOLES];
-        const LockRes lr = lock_score<false>(p.flags, f[ST_AFTER_LINES], orv, [fholes] { return fholes; }, old_holes,
-                                             old_height, rew, score, lines, holes1, height1, deaths);
-        dead1 = lr.died;
-        if (wts1) {
-            float w[NF];
-#pragma unroll
-            for (int r = 0; r < NF; ++r) {
-                w[r] = wts1[(size_t)wrow * NF + r];
-                asm volatile("" : "+v"(w[r]));  // in vector registers: the row is wave-uniform, and as scalars it spills
-            }
-            s1score = lin_score(w, f);
-        }
-        if (live) {
-            sHoles[s1] = holes1;
-            sHeight[s1] = height1;
-        }
-        const uint64_t lm = __ballot(cand && !dead1);
-        if (lane == 0) {
-            sLive[wave][0] = (uint32_t)lm;
-            sLive[wave][1] = (uint32_t)(lm >> 32);
-        }
-    } else if (lane == 0) {
-        sLive[wave][0] = sLive[wave][1] = 0u;
-    }
-    __syncthreads();
-
-    // ---- second ply: the live s1, round-robin over the waves; lane = s2 ----
-    {
-        float w[NF];
-#pragma unroll
-        for (int r = 0; r < NF; ++r) {
-            w[r] = wts2[(size_t)wrow * NF + r];
-            asm volatile("" : "+v"(w[r]));  // (as in the first ply)
-        }
-        int k = 0;
-        for (int q = 0; q < kLaWaves; ++q) {
-            uint64_t m = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)sLive[q][0]) |
-                         (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)sLive[q][1]) << 32;
-            for (; m; m &= m - 1) {
-                if ((k++ & (kLaWaves - 1)) != wave) continue;
-                const int s1 = q * kWave + (int)__builtin_ctzll(m);
-                const uint32_t *C = B1 + s1 * pitch + kAfterP;
-                const int32_t h1 = sHoles[s1], g1 = sHeight[s1];
-                int32_t bslot;
-                float bscore;
-                auto pass = [&](int s0, auto first) {
-                    const int s = s0 + lane;
-                    const bool live = s < S;
-                    int32_t f[NF];
-                    const bool valid = eval_slot_set<SET>(C, W, H, p.flags, nid, live ? s : S - 1, h1, g1, f,
-                                                          [](int, uint32_t, bool) {});
-                    const float sc = lin_score(w, f);
-                    if constexpr (decltype(first)::value) {  // (the score is read only where bslot >= 0)
-                        bslot = live && valid ? s : -1;
-                        bscore = sc;
-                    } else if (live && valid && (bslot < 0 || sc > bscore)) {
-                        bslot = s;
-                        bscore = sc;
-                    }
-                };
-                pass(0, PassTag<true>{});
-                for (int s0 = kWave; s0 < S; s0 += kWave) pass(s0, PassTag<false>{});
-                // k_policy_linear_set's reductions: the maximum, then the lowest slot that reaches it
-                const bool has = bslot >= 0;
-                const float top =
-                    __int_as_float(wave_reduce(__float_as_int(has ? bscore : -__builtin_inff()), [](int a, int b) {
-                        return __float_as_int(__builtin_fmaxf(__int_as_float(a), __int_as_float(b)));
-                    }));
-                bool tied = has && bscore == top;
-                if (__ballot(tied) == 0) tied = has;
-                const int32_t win = wave_reduce(tied ? bslot : INT32_MAX, [](int a, int b) { return a < b ? a : b; });
-                if (lane == 0) {
-                    sM2[s1] = top;
-                    sSl2[s1] = win == INT32_MAX ? -1 : win;
-                }
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- choose ----
-    if (active) {
-        const bool live = t < S;
-        const int32_t sl2 = cand && !dead1 ? sSl2[live ? t : 0] : -1;
-        const float tail = sl2 >= 0 ? sM2[live ? t : 0] : dead_value;
-        const float tot = s1score + tail;
-        if (live) {
-            if (scores_all) scores_all[(size_t)e * S + t] = cand ? tot : 0.0f;
-            if (slots2_all) slots2_all[(size_t)e * S + t] = cand ? sl2 : -1;
-        }
-        const float top = __int_as_float(wave_reduce(__float_as_int(cand ? tot : -__builtin_inff()), [](int a, int b) {
-            return __float_as_int(__builtin_fmaxf(__int_as_float(a), __int_as_float(b)));
-        }));
-        bool tied = cand && tot == top;
-        if (__ballot(tied) == 0) tied = cand;
-        const int32_t win = wave_reduce(tied ? t : INT32_MAX, [](int a, int b) { return a < b ? a : b; });
-        if (win == INT32_MAX ? lane == 0 : tied && t == win) {
-            sWin[wave] = win == INT32_MAX ? -1 : win;
-            sWin2[wave] = sl2;
-            sTop[wave] = tot;
-        }
-    } else if (lane == 0) {
-        sWin[wave] = -1;
-    }
-    __syncthreads();
-    if (t == 0) {
-        int32_t win = -1, win2 = -1;
-        float top = 0.0f;
-        for (int q = 0; q < kLaWaves; ++q) {  // the first wave with the largest score: ties to the lowest s1
-            if (sWin[q] >= 0 && (win < 0 || sTop[q] > top)) {
-                win = sWin[q];
-                win2 = sWin2[q];
-                top = sTop[q];
-            }
-        }
-        const bool none = win < 0;
-        const int trot = (win >= per) + (win >= 2 * per) + (win >= 3 * per), tx = win - trot * per - 3;
-        if (slots) slots[e] = win;
-        if (slots2) slots2[e] = win2;
-        if (scores) scores[e] = none ? 0.0f : top;
-        if (actions) {
-            const int rot = (int)((pw >> 3) & 3u), ax = (int)((pw >> 5) & 63u);
-            // k_placement_actions's rule
-            actions[e] = (uint8_t)(none ? 2u : rot != trot ? 4u : (ax < tx ? 1u : (ax > tx ? 0u : 2u)));
-        }
-        if constexpr (COMMIT) {
-            if (!none) p.piece[e] = placed_piece(id, trot, tx, p.lock_mod);
-        }
-    }
-}
-#endif  // ST_LOOKAHEAD_TU
-
-#ifdef ST_EXPECT_TU
-// ---------------------------------------------------------------- piece odds, expectimax player
-// st_next_weights: m of _choose_shape (tetris_env.py:186) from the counter rows
-// of the moment, m[i] = 5 + max(counts) - counts[i] -- the odds of the piece the
-// env's next _new_piece takes (shape_counts changes only at a spawn and clear()
-// keeps it: k_next_piece's argument).  The MT row is not read.  Unsigned
-// arithmetic: host-written counts of any size wrap, they do not trap.
-__device__ __forceinline__ void next_odds(const int32_t (&cnt)[7], uint32_t (&m)[7]) {
-    int32_t maxc = cnt[0];
-#pragma unroll
-    for (int i = 1; i < 7; ++i) maxc = cnt[i] > maxc ? cnt[i] : maxc;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) m[i] = 5u + (uint32_t)maxc - (uint32_t)cnt[i];
-}
-
-// One lane per env; out int32 [7][n], env innermost.
-__global__ __launch_bounds__(256) void k_next_weights(KParams p, int32_t *__restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.n) return;
-    int32_t cnt[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) cnt[i] = p.stats[(ST_STAT_COUNT0 + i) * p.stride + e];
-    uint32_t m[7];
-    next_odds(cnt, m);
-#pragma unroll
-    for (int i = 0; i < 7; ++i) out[(int64_t)i * p.n + e] = (int32_t)m[i];
-}
-
-// E(s1) of st_policy_expect: acc = acc + (float)m[q] * T[q] over q = 0..6 from
-// 0.0f, then acc / (float)M, every product, every sum and the division rounded
-// on their own -- lin_score's precautions for the products; `/` is the
-// correctly rounded division under the project's flags (v_div_scale /
-// v_div_fmas / v_div_fixup in the code object; DESIGN.md "Expectimax player").
-__device__ __forceinline__ float expect_chain(const uint32_t (&m)[7], uint32_t M, const float (&T)[7]) {
-#pragma clang fp contract(off)
-    float acc = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 7; ++q) {
-        float prod = (float)m[q] * T[q];
-        asm volatile("" : "+v"(prod));  // the rounded product, opaque to the add below
-        acc = acc + prod;
-    }
-    float e = acc / (float)M;
-    asm volatile("" : "+v"(e));  // the rounded quotient, opaque to the caller's add
-    return e;
-}
-
-// st_policy_expect: the two-ply player over the odds of the next piece
-// (simpletetris.h, "Expectimax player").  k_policy_lookahead's shape -- one
-// workgroup of kLaWaves waves per env, the same staging, the same first ply
-// with thread = s1 and B1[s1][] in LDS, the same live ballots -- with these
-// differences:
-//  - no preview is read: the seven counter rows give m (next_odds);
-//  - second ply: the tasks are the pairs (live s1, q), q = 0..6, numbered
-//    7 * k + q for the k-th live s1 in slot order and taken round-robin by the
-//    waves (task i goes to wave i % kLaWaves); lane = s2, ceil(S / 64) passes of
-//    eval_slot_set on B1[s1] with piece q (wave-uniform) and X(s1)'s counters,
-//    lin_score, the two wave_reduces: T_q(s1) and its lowest s2 to sT / sSl2,
-//    [7][kLaSlots] each;
-//  - choose: after the barrier thread t reads its seven tails (dead_value where
-//    s1 is dead or a piece has no valid s2), writes its table entries, runs
-//    expect_chain and adds S1; the rest is k_policy_lookahead's.
-template <int SET, bool COMMIT>
-__global__ __launch_bounds__(kLaWaves *kWave) void k_policy_expect(
-    KParams p, const float *__restrict__ wts1, const float *__restrict__ wts2, int64_t n_w, float dead_value,
-    const int32_t *__restrict__ allowed, int32_t *__restrict__ slots, uint8_t *__restrict__ actions,
-    float *__restrict__ scores, float *__restrict__ scores_all, float *__restrict__ tails,
-    int32_t *__restrict__ slots2_all) {
-    constexpr int NF = feat_rows(SET);
-    // (the output pointers wait in vector registers for the last phase, as in k_policy_lookahead)
-    asm volatile("" : "+v"(slots), "+v"(actions), "+v"(scores), "+v"(scores_all), "+v"(tails), "+v"(slots2_all));
-    extern __shared__ uint32_t B1[];  // [S][la_pitch(W)]
-    __shared__ uint32_t L[kAfterCols];
-    __shared__ int32_t sHoles[kLaSlots], sHeight[kLaSlots], sSl2[7][kLaSlots];
-    __shared__ float sT[7][kLaSlots];
-    __shared__ uint32_t sLive[kLaWaves][2];
-    __shared__ float sTop[kLaWaves];
-    __shared__ int32_t sWin[kLaWaves];
-    const int t = threadIdx.x, lane = t & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int64_t e = blockIdx.x;  // the grid is p.n workgroups: padding envs are not evaluated
-    const int64_t sd = p.stride;
-    const int W = p.W, H = p.H;
-    const int per = W + 6, S = 4 * per, pitch = la_pitch(W);
-    const uint32_t floorb = ~((1u << H) - 1u);
-    stage_env_columns(L, p, e, t);
-    const uint32_t pw = p.piece[e];
-    const uint32_t pid = pw & 7u;
-    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
-    const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
-    const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd + e];
-    // e < 2^24 (st_create), so the row index is 32-bit arithmetic
-    const uint32_t wrow = n_w > e ? (uint32_t)e : (uint32_t)e % (uint32_t)n_w;
-    __syncthreads();
-
-    // ---- first ply: s1 = t (k_policy_lookahead's) ----
-    const bool active = wave * kWave < S;  // (wave-uniform)
-    bool cand = false, dead1 = false;
-    float s1score = 0.0f;
-    if (active) {
-        const bool live = t < S;
-        const int s1 = live ? t : S - 1;  // (threads past the last slot compute it again, store nothing)
-        uint32_t *row = B1 + s1 * pitch;
-        if (live) {
-#pragma unroll
-            for (int j = 0; j < kAfterP; ++j) row[j] = row[kAfterP + W + j] = ~0u;
-        }
-        int32_t f[NF];
-        uint32_t orv = 0;
-        const bool valid = eval_slot_set<SET>(L + kAfterP, W, H, p.flags, id, s1, old_holes, old_height, f,
-                                              [&](int c, uint32_t w, bool) {
-                                                  orv |= w;
-                                                  if (live) row[kAfterP + c] = w | floorb;
-                                              });
-        cand = live && valid && (!allowed || allowed[(size_t)e * S + s1] != 0);
-        // the counters the lock of s1 leaves (:283-297): lock_score's, on the slot's rows
-        int32_t rew = 0, score = 0, lines = 0, holes1 = old_holes, height1 = old_height, deaths = 0;
-        const int32_t fholes = f[ST_AFTER_HOLES];
-        const LockRes lr = lock_score<false>(p.flags, f[ST_AFTER_LINES], orv, [fholes] { return fholes; }, old_holes,
-                                             old_height, rew, score, lines, holes1, height1, deaths);
-        dead1 = lr.died;
-        if (wts1) {
-            float w[NF];
-#pragma unroll
-            for (int r = 0; r < NF; ++r) {
-                w[r] = wts1[(size_t)wrow * NF + r];
-                asm volatile("" : "+v"(w[r]));  // in vector registers: the row is wave-uniform, and as scalars it spills
-            }
-            s1score = lin_score(w, f);
-        }
-        if (live) {
-            sHoles[s1] = holes1;
-            sHeight[s1] = height1;
-        }
-        const uint64_t lm = __ballot(cand && !dead1);
-        if (lane == 0) {
-            sLive[wave][0] = (uint32_t)lm;
-            sLive[wave][1] = (uint32_t)(lm >> 32);
-        }
-    } else if (lane == 0) {
-        sLive[wave][0] = sLive[wave][1] = 0u;
-    }
-    __syncthreads();
-
-    // ---- second ply: the tasks (live s1, q), round-robin over the waves; lane = s2 ----
-    {
-        float w[NF];
-#pragma unroll
-        for (int r = 0; r < NF; ++r) {
-            w[r] = wts2[(size_t)wrow * NF + r];
-            asm volatile("" : "+v"(w[r]));  // (as in the first ply)
-        }
-        int k = 0;
-        for (int qw = 0; qw < kLaWaves; ++qw) {
-            uint64_t lm = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)sLive[qw][0]) |
-                          (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)sLive[qw][1]) << 32;
-            for (; lm; lm &= lm - 1) {
-                const int s1 = qw * kWave + (int)__builtin_ctzll(lm);
-                const uint32_t *C = B1 + s1 * pitch + kAfterP;
-                for (int q = 0; q < 7; ++q) {
-                    if ((k++ & (kLaWaves - 1)) != wave) continue;
-                    const int32_t h1 = sHoles[s1], g1 = sHeight[s1];
-                    int32_t bslot;
-                    float bscore;
-                    auto pass = [&](int s0, auto first) {
-                        const int s = s0 + lane;
-                        const bool live = s < S;
-                        int32_t f[NF];
-                        const bool valid = eval_slot_set<SET>(C, W, H, p.flags, q, live ? s : S - 1, h1, g1, f,
-                                                              [](int, uint32_t, bool) {});
-                        const float sc = lin_score(w, f);
-                        if constexpr (decltype(first)::value) {  // (the score is read only where bslot >= 0)
-                            bslot = live && valid ? s : -1;
-                            bscore = sc;
-                        } else if (live && valid && (bslot < 0 || sc > bscore)) {
-                            bslot = s;
-                            bscore = sc;
-                        }
-                    };
-                    pass(0, PassTag<true>{});
-                    for (int s0 = kWave; s0 < S; s0 += kWave) pass(s0, PassTag<false>{});
-                    // k_policy_linear_set's reductions: the maximum, then the lowest slot that reaches it
-                    const bool has = bslot >= 0;
-                    const float top =
-                        __int_as_float(wave_reduce(__float_as_int(has ? bscore : -__builtin_inff()), [](int a, int b) {
-                            return __float_as_int(__builtin_fmaxf(__int_as_float(a), __int_as_float(b)));
-                        }));
-                    bool tied = has && bscore == top;
-                    if (__ballot(tied) == 0) tied = has;
-                    const int32_t win =
-                        wave_reduce(tied ? bslot : INT32_MAX, [](int a, int b) { return a < b ? a : b; });
-                    if (lane == 0) {
-                        sT[q][s1] = top;
-                        sSl2[q][s1] = win == INT32_MAX ? -1 : win;
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- choose ----
-    if (active) {
-        const bool live = t < S, open = cand && !dead1;
-        const int ti = live ? t : 0;
-        int32_t cnt[7];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) cnt[q] = p.stats[(ST_STAT_COUNT0 + q) * sd + e];
-        uint32_t m[7], M = 0;
-        next_odds(cnt, m);
-#pragma unroll
-        for (int q = 0; q < 7; ++q) M += m[q];
-        float T[7];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) {
-            const int32_t sl2 = open ? sSl2[q][ti] : -1;
-            T[q] = sl2 >= 0 ? sT[q][ti] : dead_value;
-            if (live) {
-                if (tails) tails[((size_t)e * 7 + q) * S + t] = cand ? T[q] : 0.0f;
-                if (slots2_all) slots2_all[((size_t)e * 7 + q) * S + t] = cand ? sl2 : -1;
-            }
-        }
-        const float tot = s1score + expect_chain(m, M, T);
-        if (live && scores_all) scores_all[(size_t)e * S + t] = cand ? tot : 0.0f;
-        const float top = __int_as_float(wave_reduce(__float_as_int(cand ? tot : -__builtin_inff()), [](int a, int b) {
-            return __float_as_int(__builtin_fmaxf(__int_as_float(a), __int_as_float(b)));
-        }));
-        bool tied = cand && tot == top;
-        if (__ballot(tied) == 0) tied = cand;
-        const int32_t win = wave_reduce(tied ? t : INT32_MAX, [](int a, int b) { return a < b ? a : b; });
-        if (win == INT32_MAX ? lane == 0 : tied && t == win) {
-            sWin[wave] = win == INT32_MAX ? -1 : win;
-            sTop[wave] = tot;
-        }
-    } else if (lane == 0) {
-        sWin[wave] = -1;
-    }
-    __syncthreads();
-    if (t == 0) {
-        int32_t win = -1;
-        float top = 0.0f;
-        for (int q = 0; q < kLaWaves; ++q) {  // the first wave with the largest score: ties to the lowest s1
-            if (sWin[q] >= 0 && (win < 0 || sTop[q] > top)) {
-                win = sWin[q];
-                top = sTop[q];
-            }
-        }
-        const bool none = win < 0;
-        const int trot = (win >= per) + (win >= 2 * per) + (win >= 3 * per), tx = win - trot * per - 3;
-        if (slots) slots[e] = win;
-        if (scores) scores[e] = none ? 0.0f : top;
-        if (actions) {
-            const int rot = (int)((pw >> 3) & 3u), ax = (int)((pw >> 5) & 63u);
-            // k_placement_actions's rule
-            actions[e] = (uint8_t)(none ? 2u : rot != trot ? 4u : (ax < tx ? 1u : (ax > tx ? 0u : 2u)));
-        }
-        if constexpr (COMMIT) {
-            if (!none) p.piece[e] = placed_piece(id, trot, tx, p.lock_mod);
-        }
-    }
-}
-#endif  // ST_EXPECT_TU
-
-// (st_routes.hip and st_locks.hip share reach_free / reach_fall)
-#if defined(ST_REACHABLE_TU) || defined(ST_ROUTES_TU) || defined(ST_LOCKS_TU)
-// ---------------------------------------------------------------- reachability
-// st_reachable / st_route_actions: which placement slots of st_afterstates the
-// live piece can really be locked in under TetrisEngine.step
-// (tetris_env.py:243-304), in how many steps, and the first action of a
-// shortest way there (simpletetris.h, "Reachability").  A breadth-first search
-// over the piece states (rot, x, y, l) with the board fixed, whole sets at a
-// time: one wave per env, a lane per slot (rot, x) as in k_afterstates,
-// ceil(S / 64) slots a lane; a lane's 32-bit word is a set of anchor rows y
-// (never negative, below H <= 28).
-//   free[rot, x]  bit y: the piece at (x, y) is not is_occupied (:29-36) -- the
-//                 four box columns shifted by each cell's dy, ORed, inverted;
-//                 rows above 0 shift in zeros (free, :32-33), rows past the
-//                 field read the floor bits, columns past it the walls.  Every
-//                 shape holds cell (0, 0), so no bit y >= H and no column
-//                 outside [0, W) is ever free: nothing crosses a row's edge.
-//   sets          A[tag][l][slot] in LDS, l = the lock counter's plane; two
-//                 copies, read one / write the other, one wave_sync a layer.
-// One layer = one step applied to a whole set: every action's destinations
-// (a neighbouring lane's word & free for left / right / the two rotations,
-// (A << 1) & free for soft drop, an occluded fill downward -- Kogge-Stone,
-// five rounds -- for hard drop, A itself for idle and for every refused
-// action), then gravity (:247-250), then _has_dropped and the lock counter
-// (:259-262) across the planes.  Sets are cumulative, so the first layer whose
-// lock set holds a slot's landing bit is its distance; the loop ends on a
-// wave-uniform ballot when no set grew (then no lock set can grow either), and
-// in every case after 4 * (W + 6) * H * (L + 1) layers, the number of states.
-// TAGGED: seven sets, started from the seven successors of the start state
-// (layer 1, computed by lanes 0..6 on the start state alone); the lowest tag
-// that reaches a slot at its first layer is `first`.  ROUTE: the tagged search
-// with one target slot an env, ended as soon as any tag reaches it.
-__device__ __forceinline__ uint32_t reach_free(const uint32_t *C, int W, int id, int s) {
-    const int per = W + 6;
-    const int r = (s >= per) + (s >= 2 * per) + (s >= 3 * per), x = s - r * per - 3;
-    const uint32_t m = c_tab_m[id * 4 + r], g = c_tab_g[id * 4 + r];
-    const int x0 = box_x0(g, x);  // in [-6, W + 2]
-    uint32_t occ = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t col = C[x0 + j], byte = (m >> (8 * j)) & 0xFFu;
-#pragma unroll
-        for (int b = 0; b < 7; ++b)  // bit b: a cell at dy = b - 3
-            if ((byte >> b) & 1u) occ |= b >= 3 ? col >> (b - 3) : col << (3 - b);
-    }
-    return ~occ;
-}
-
-// Every row a set's pieces can fall to (hard_drop's loop, :54-59, on all of
-// them at once): bit y + 1 joins while its row is free.
-__device__ __forceinline__ uint32_t reach_fall(uint32_t a, uint32_t free) {
-    uint32_t gen = a, pro = free;
-    gen |= pro & (gen << 1);
-    pro &= pro << 1;
-    gen |= pro & (gen << 2);
-    pro &= pro << 2;
-    gen |= pro & (gen << 4);
-    pro &= pro << 4;
-    gen |= pro & (gen << 8);
-    pro &= pro << 8;
-    gen |= pro & (gen << 16);
-    return gen;
-}
-
-constexpr uint32_t kReachNone = ~0u;  // a result word (layer << 3 | tag) not found yet
-
-template <bool TAGGED, bool ROUTE>
-__global__ __launch_bounds__(kWave) void k_reachable(KParams p, const int32_t *__restrict__ slots,
-                                                     int32_t *__restrict__ steps_out,
-                                                     uint8_t *__restrict__ first_out) {
-    extern __shared__ uint32_t reach_lds[];
-    constexpr int NT = TAGGED ? 7 : 1;
-    const int lane = threadIdx.x;
-    const int64_t e = blockIdx.x;  // the grid is p.n waves
-    const int W = p.W, per = W + 6, S = 4 * per;
-    const int NP = p.lock_mod;  // planes: lock counter 0 .. L (the launcher checked L <= ST_REACH_MAX_LOCK)
-    const bool sreset = (p.flags & ST_STEP_RESET) != 0u;
-    uint32_t *const C = reach_lds;       // column words
-    uint32_t *const F = C + kAfterCols;  // [S] free rows
-    uint32_t *const T = F + S;           // [S] the landing bit of a valid (ROUTE: the target) slot, else 0
-    uint32_t *const R = T + S;           // [S] layer << 3 | tag of the first lock there
-    uint32_t *const A = R + S;           // [2][NT][NP][S]
-    const int setw = NT * NP * S;
-
-    stage_env_columns(C, p, e, lane);
-    const uint32_t pw = p.piece[e];
-    const uint32_t pid = pw & 7u;
-    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
-    const int rot = (int)((pw >> 3) & 3u), cx0 = (int)((pw >> 5) & 63u) + 3, ay = (int)((pw >> 11) & 63u);
-    const int lock0 = (int)(pw >> 17) < NP ? (int)(pw >> 17) : NP - 1;  // (a host-written counter above L: unspecified)
-    // a start outside the lane grid or the row word (host-written) can only lock where it is: no slot
-    const bool start_ok = cx0 < per && ay < 32;
-    int tgt = -1;
-    if constexpr (ROUTE) {
-        tgt = slots[e];
-        if (tgt < 0 || tgt >= S) tgt = -1;
-    }
-    wave_sync();
-    for (int s = lane; s < S; s += kWave) {
-        const uint32_t f = reach_free(C + kAfterP, W, id, s);
-        F[s] = f;
-        // valid: free at row 0; the landing row: the last free row of the run from row 0
-        T[s] = (f & 1u) && (!ROUTE || s == tgt) ? 1u << (__builtin_ctz(~f) - 1) : 0u;
-        R[s] = kReachNone;
-        for (int k = 0; k < NT * NP; ++k) A[k * S + s] = 0u;
-    }
-    wave_sync();
-    bool search = start_ok;
-    if constexpr (ROUTE) search = search && tgt >= 0 && T[tgt] != 0u;
-
-    auto is_free = [&](int r, int cx, int y) -> bool {
-        return cx >= 0 && cx < per && y < 32 && ((F[r * per + cx] >> y) & 1u);
-    };
-    if (search) {
-        if constexpr (TAGGED) {
-            if (lane < 7) {  // layer 1: action `lane` on the start state (:245-262)
-                int r = rot, cx = cx0, y = ay, l = lock0;
-                if (lane == 0) cx -= is_free(r, cx - 1, y) ? 1 : 0;
-                else if (lane == 1) cx += is_free(r, cx + 1, y) ? 1 : 0;
-                else if (lane == 2) y += __builtin_ctz(~(y < 31 ? F[r * per + cx] >> (y + 1) : 0u));
-                else if (lane == 3) y += is_free(r, cx, y + 1) ? 1 : 0;
-                else if (lane == 4) r = is_free((r + 1) & 3, cx, y) ? (r + 1) & 3 : r;
-                else if (lane == 5) r = is_free((r + 3) & 3, cx, y) ? (r + 3) & 3 : r;
-                if (is_free(r, cx, y + 1)) {
-                    ++y;
-                    l = sreset ? 0 : l;
-                }
-                const int s1 = r * per + cx;
-                bool locked = false;
-                if (!is_free(r, cx, y + 1)) {
-                    l = l + 1 == NP ? 0 : l + 1;
-                    locked = l == 0;
-                }
-                if (!locked) A[(lane * NP + l) * S + s1] = 1u << y;
-                else if (T[s1] & (1u << y)) atomicMin(&R[s1], 1u << 3 | (uint32_t)lane);
-            }
-        } else {
-            if (lane == 0) A[lock0 * S + rot * per + cx0] = 1u << ay;
-        }
-    }
-    wave_sync();
-    if constexpr (ROUTE) search = search && R[tgt < 0 ? 0 : tgt] == kReachNone;
-
-    int cur = 0;
-    const int max_layer = search ? 4 * per * p.H * NP : 0;
-    for (int layer = TAGGED ? 2 : 1; layer <= max_layer; ++layer) {
-        const uint32_t *const In = A + cur * setw;
-        uint32_t *const Out = A + (cur ^ 1) * setw;
-        bool grew = false, hit = false;
-        for (int s = lane; s < S; s += kWave) {
-            const uint32_t f = F[s], fd = f >> 1, tb = T[s];  // fd: the row below is free
-            // (the first and the last slot are never free: what they read in is masked away)
-            const int sl = s > 0 ? s - 1 : 0, sr = s < S - 1 ? s + 1 : s;
-            const int su = s + per < S ? s + per : s + per - S, sd = s >= per ? s - per : s - per + S;
-            for (int tag = 0; tag < NT; ++tag) {
-                const uint32_t *const It = In + tag * NP * S;
-                uint32_t *const Ot = Out + tag * NP * S;
-                uint32_t mvall = 0;
-                for (int l = 0; l < NP; ++l) {  // the action: every destination of plane l
-                    const uint32_t *const I = It + l * S;
-                    const uint32_t a = I[s];
-                    const uint32_t nb = I[sl] | I[sr] | I[su] | I[sd];
-                    const uint32_t pos = a | ((nb | (a << 1)) & f) | (reach_fall(a, f) & ~fd);
-                    Ot[l * S + s] = pos;  // (the lane's own word: read back below)
-                    mvall |= (pos << 1) & f;
-                }
-                uint32_t grounded = 0;  // of the plane below: its counter moves up to this one
-                for (int l = 0; l < NP; ++l) {  // gravity, then _has_dropped and the counter
-                    const uint32_t pos = Ot[l * S + s];
-                    const uint32_t moved = sreset ? (l == 0 ? mvall : 0u) : (pos << 1) & f;
-                    const uint32_t g = (pos & ~fd) | moved;
-                    const uint32_t old = It[l * S + s];
-                    const uint32_t nw = old | (g & fd) | grounded;
-                    Ot[l * S + s] = nw;
-                    grew = grew || nw != old;
-                    grounded = g & ~fd;
-                }
-                // `grounded` of the last plane: the counter wraps to 0, the piece locks
-                if ((grounded & tb) && R[s] == kReachNone) {
-                    R[s] = (uint32_t)layer << 3 | (uint32_t)tag;
-                    hit = true;
-                }
-            }
-        }
-        wave_sync();
-        cur ^= 1;
-        if (ROUTE && __ballot(hit)) break;
-        if (!__ballot(grew)) break;
-    }
-
-    if constexpr (ROUTE) {
-        if (lane == 0) {
-            const uint32_t r = tgt < 0 ? kReachNone : R[tgt];
-            first_out[e] = (uint8_t)(r == kReachNone ? 2u : r & 7u);
-            if (steps_out) steps_out[e] = r == kReachNone ? 0 : (int32_t)(r >> 3);
-        }
-    } else {
-        const size_t base = (size_t)e * S;
-        for (int s = lane; s < S; s += kWave) {
-            const uint32_t r = R[s];
-            steps_out[base + s] = r == kReachNone ? 0 : (int32_t)(r >> 3);
-            if constexpr (TAGGED) first_out[base + s] = (uint8_t)(r == kReachNone ? 2u : r & 7u);
-        }
-    }
-}
-#endif  // ST_REACHABLE_TU || ST_ROUTES_TU
-
-#if defined(ST_ROUTES_TU) || defined(ST_LOCKS_TU)  // (st_locks.hip shares route_rise and the route constants)
-// ---------------------------------------------------------------- routes
-// st_routes / st_policy_routed / st_play_routed: the whole shortest route of
-// the live piece into a slot (simpletetris.h, "Routes"), planned once a piece.
-// One wave per env, a lane per slot, whole-row bit sets, as k_reachable; an
-// env that is not needed leaves after one load, on a wave-uniform test.
-//  (a) forward   k_reachable's untagged search: R[s] != kReachNone iff slot s
-//                is reachable (the planner only).
-//  (b) choice    k_policy_linear_set's pass over the slots -- eval_slot_set,
-//                lin_score, the two wave_reduces -- with R as the mask (the
-//                planner only; st_routes reads its target instead).
-//  (c) backward  B[l][s]: the states with D <= layer, D(x) the length of the
-//                shortest sequence from x that locks at the target's landing.
-//                A layer evaluates the step rule on every state at once:
-//                  E[l]  a piece that ARRIVES at (s, y) in plane l after
-//                        gravity ends well: in the air it must be in B[l], on
-//                        the ground in B[l + 1] -- or, from the last plane, at
-//                        the target's landing (the lock);
-//                  Q[l]  a piece that stands at (s, y) in plane l after the
-//                        ACTION ends well: gravity moves it a row (to plane 0
-//                        under step_reset) where the row below is free;
-//                  P[l]  some action ends well: Q itself (idle and every
-//                        refused action), a neighbour's Q where the neighbour
-//                        is free (left / right / the two rotations), Q a row
-//                        down (soft drop), and the upward occluded fill of the
-//                        grounded rows of Q (hard drop: route_rise, the mirror
-//                        of reach_fall).
-//                A state that joins B at layer k gets D = k in a uint16 per
-//                state (D[l][s][32]).  The search ends when the start state
-//                joins (its layer is steps[s]) or when no set grew.
-//  (d) walk      from the start state, at most ST_ROUTE_MAX times: lanes 0..6
-//                apply one action each (k_reachable's layer-1 rule), a ballot
-//                picks the lowest whose successor has D one lower (for D = 1:
-//                that locks at the landing), its state is the next.
-// LDS: column words, F and R, two copies of the forward sets -- reused as B and
-// Q --, and D: 4 * (48 + 2 S + 2 (L + 1) S) + 64 (L + 1) S bytes.
-constexpr uint64_t kRouteNone = 0x7FFFFFFFFFFFFFFFull;  // every field 7, bit 63 clear
-constexpr int kRoutePlanes = ST_REACH_MAX_LOCK + 1;
-
-// Every row from which a hard drop lands in a row of `a` (rows of `a` are
-// grounded): row y joins while row y + 1 is free (fd bit y) and has joined.
-__device__ __forceinline__ uint32_t route_rise(uint32_t a, uint32_t fd) {
-    uint32_t gen = a, pro = fd;
-    gen |= pro & (gen >> 1);
-    pro &= pro >> 1;
-    gen |= pro & (gen >> 2);
-    pro &= pro >> 2;
-    gen |= pro & (gen >> 4);
-    pro &= pro >> 4;
-    gen |= pro & (gen >> 8);
-    pro &= pro >> 8;
-    gen |= pro & (gen >> 16);
-    return gen;
-}
-
-struct RouteIO {
-    const int32_t *slots_in;  // st_routes: the targets int32 [n]
-    const uint8_t *need;      // uint8 [n] or null: every env
-    int32_t *rem;             // st_play_routed: an env is needed iff rem[e] == 0, and gets min(steps, ST_ROUTE_MAX)
-    const float *wts;         // the planner: float [n_w][rows]
-    int64_t n_w;
-    int32_t *slots;           // the planner: the chosen slot int32 [n]
-    uint64_t *route;          // uint64 [ST_ROUTE_WORDS][n]
-    int32_t *steps;           // int32 [n] or null
-    float *scores;            // the planner: float [n] or null
-};
-
-// SET: a feature set -- the planner, (a) to (d); -1 -- st_routes, (c) and (d) for slots_in[e]
-template <int SET>
-__global__ __launch_bounds__(kWave) void k_routes(KParams p, RouteIO io) {
-    extern __shared__ uint32_t route_lds[];
-    const int lane = threadIdx.x;
-    const int64_t e = blockIdx.x;  // the grid is p.n waves
-    if (io.rem ? io.rem[e] != 0 : (io.need != nullptr && io.need[e] == 0)) return;  // (wave-uniform)
-    const int W = p.W, H = p.H, per = W + 6, S = 4 * per;
-    const int NP = p.lock_mod;  // planes: lock counter 0 .. L (the host checked L <= ST_REACH_MAX_LOCK)
-    const bool sreset = (p.flags & ST_STEP_RESET) != 0u;
-    uint32_t *const C = route_lds;       // column words
-    uint32_t *const F = C + kAfterCols;  // [S] free rows
-    uint32_t *const R = F + S;           // [S] the forward search's first lock layer
-    uint32_t *const A = R + S;           // [2][NP][S]
-    uint16_t *const D = reinterpret_cast<uint16_t *>(A + 2 * NP * S);  // [NP][S][32]
-    const int setw = NP * S;
-
-    stage_env_columns(C, p, e, lane);
-    const uint32_t pw = p.piece[e];
-    const uint32_t pid = pw & 7u;
-    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
-    const int rot = (int)((pw >> 3) & 3u), cx0 = (int)((pw >> 5) & 63u) + 3, ay = (int)((pw >> 11) & 63u);
-    const int lock0 = (int)(pw >> 17) < NP ? (int)(pw >> 17) : NP - 1;  // (as k_reachable reads it)
-    const bool start_ok = cx0 < per && ay < 32;  // (k_reachable: such a start reaches no slot)
-    wave_sync();
-    for (int s = lane; s < S; s += kWave) {
-        F[s] = reach_free(C + kAfterP, W, id, s);
-        R[s] = kReachNone;
-        for (int k = 0; k < 2 * NP; ++k) A[k * S + s] = 0u;
-    }
-    wave_sync();
-    auto is_free = [&](int r, int cx, int y) -> bool {
-        return cx >= 0 && cx < per && y < 32 && ((F[r * per + cx] >> y) & 1u);
-    };
-
-    int tgt = -1;
-    if constexpr (SET >= 0) {
-        // (a) k_reachable<false, false>'s layers, its result words in R
-        if (start_ok && lane == 0) A[lock0 * S + rot * per + cx0] = 1u << ay;
-        wave_sync();
-        int cur = 0;
-        const int max_fwd = start_ok ? 4 * per * H * NP : 0;
-        for (int layer = 1; layer <= max_fwd; ++layer) {
-            const uint32_t *const In = A + cur * setw;
-            uint32_t *const Out = A + (cur ^ 1) * setw;
-            bool grew = false;
-            for (int s = lane; s < S; s += kWave) {
-                const uint32_t f = F[s], fd = f >> 1;
-                const uint32_t tb = (f & 1u) ? 1u << (__builtin_ctz(~f) - 1) : 0u;  // a valid slot's landing
-                const int sl = s > 0 ? s - 1 : 0, sr = s < S - 1 ? s + 1 : s;
-                const int su = s + per < S ? s + per : s + per - S, sd = s >= per ? s - per : s - per + S;
-                uint32_t mvall = 0;
-                for (int l = 0; l < NP; ++l) {
-                    const uint32_t *const I = In + l * S;
-                    const uint32_t a = I[s];
-                    const uint32_t nb = I[sl] | I[sr] | I[su] | I[sd];
-                    const uint32_t pos = a | ((nb | (a << 1)) & f) | (reach_fall(a, f) & ~fd);
-                    Out[l * S + s] = pos;
-                    mvall |= (pos << 1) & f;
-                }
-                uint32_t grounded = 0;
-                for (int l = 0; l < NP; ++l) {
-                    const uint32_t pos = Out[l * S + s];
-                    const uint32_t moved = sreset ? (l == 0 ? mvall : 0u) : (pos << 1) & f;
-                    const uint32_t g = (pos & ~fd) | moved;
-                    const uint32_t old = In[l * S + s];
-                    const uint32_t nw = old | (g & fd) | grounded;
-                    Out[l * S + s] = nw;
-                    grew = grew || nw != old;
-                    grounded = g & ~fd;
-                }
-                if ((grounded & tb) && R[s] == kReachNone) R[s] = (uint32_t)layer << 3;
-            }
-            wave_sync();
-            cur ^= 1;
-            if (!__ballot(grew)) break;
-        }
-
-        // (b) k_policy_linear_set's choice, the mask being R
-        constexpr int NF = feat_rows(SET);
-        const int64_t sd_ = p.stride;
-        const int32_t old_holes = p.stats[ST_STAT_HOLES * sd_ + e];
-        const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd_ + e];
-        const uint32_t wrow = io.n_w > e ? (uint32_t)e : (uint32_t)e % (uint32_t)io.n_w;
-        float w[NF];
-#pragma unroll
-        for (int r = 0; r < NF; ++r) w[r] = io.wts[(size_t)wrow * NF + r];
-        int32_t bslot = -1;
-        float bscore = 0.0f;
-        for (int s0 = 0; s0 < S; s0 += kWave) {
-            const int s = s0 + lane;
-            const bool live = s < S;
-            int32_t f[NF];
-            bool valid = eval_slot_set<SET>(C + kAfterP, W, H, p.flags, id, live ? s : S - 1, old_holes, old_height, f,
-                                            [](int, uint32_t, bool) {});
-            valid = valid && live && R[live ? s : 0] != kReachNone;
-            const float sc = lin_score(w, f);
-            if (valid && (bslot < 0 || sc > bscore)) {  // (a lane's slots ascend: the first maximum stays)
-                bslot = s;
-                bscore = sc;
-            }
-        }
-        const bool has = bslot >= 0;
-        const float top =
-            __int_as_float(wave_reduce(__float_as_int(has ? bscore : -__builtin_inff()), [](int a, int b) {
-                return __float_as_int(__builtin_fmaxf(__int_as_float(a), __int_as_float(b)));
-            }));
-        bool tied = has && bscore == top;
-        if (__ballot(tied) == 0) tied = has;  // (a NaN score equals nothing: every candidate counts)
-        const int32_t win = wave_reduce(tied ? bslot : INT32_MAX, [](int a, int b) { return a < b ? a : b; });
-        const bool none = win == INT32_MAX;
-        if (none ? lane == 0 : tied && bslot == win) {
-            io.slots[e] = none ? -1 : win;
-            if (io.scores) io.scores[e] = none ? 0.0f : bscore;
-        }
-        tgt = none ? -1 : win;
-        wave_sync();
-        for (int s = lane; s < S; s += kWave)
-            for (int k = 0; k < NP; ++k) A[k * S + s] = 0u;  // B
-        wave_sync();
-    } else {
-        tgt = io.slots_in[e];
-        if (tgt < 0 || tgt >= S) tgt = -1;
-    }
-
-    // (c) the backward layers
-    uint32_t *const B = A, *const Q = A + setw;
-    const int s_start = rot * per + (cx0 < per ? cx0 : 0);
-    const uint32_t ftgt = tgt >= 0 ? F[tgt] : 0u;
-    const bool search = start_ok && (ftgt & 1u);
-    const uint32_t tland = search ? 1u << (__builtin_ctz(~ftgt) - 1) : 0u;  // the target's landing row
-    const int max_layer = search ? 4 * per * H * NP : 0;
-    int n = 0;  // steps: the layer at which the start state joined
-    for (int layer = 1; layer <= max_layer; ++layer) {
-        for (int s = lane; s < S; s += kWave) {
-            const uint32_t fd = F[s] >> 1, tb = s == tgt ? tland : 0u;
-            uint32_t E[kRoutePlanes];
-#pragma unroll
-            for (int l = 0; l < kRoutePlanes; ++l)
-                if (l < NP) E[l] = (fd & B[l * S + s]) | (~fd & (l + 1 == NP ? tb : B[(l + 1 < NP ? l + 1 : l) * S + s]));
-#pragma unroll
-            for (int l = 0; l < kRoutePlanes; ++l)
-                if (l < NP) Q[l * S + s] = (~fd & E[l]) | (fd & ((sreset ? E[0] : E[l]) >> 1));
-        }
-        wave_sync();
-        bool grew = false;
-        for (int s = lane; s < S; s += kWave) {
-            const uint32_t fd = F[s] >> 1;
-            const int sl = s > 0 ? s - 1 : 0, sr = s < S - 1 ? s + 1 : s;
-            const int su = s + per < S ? s + per : s + per - S, sd = s >= per ? s - per : s - per + S;
-            const uint32_t fl = F[sl], fr = F[sr], fu = F[su], fdn = F[sd];
-            for (int l = 0; l < NP; ++l) {
-                const uint32_t *const Ql = Q + l * S;
-                const uint32_t q = Ql[s];
-                const uint32_t pre = q | (fl & Ql[sl]) | (fr & Ql[sr]) | (fu & Ql[su]) | (fdn & Ql[sd]) |
-                                     (fd & (q >> 1)) | route_rise(q & ~fd, fd);
-                const uint32_t old = B[l * S + s];
-                uint32_t nw = pre & ~old;
-                if (nw) {
-                    B[l * S + s] = old | nw;
-                    grew = true;
-                    do {
-                        D[((l * S + s) << 5) + __builtin_ctz(nw)] = (uint16_t)layer;
-                        nw &= nw - 1u;
-                    } while (nw);
-                }
-            }
-        }
-        wave_sync();
-        if ((B[lock0 * S + s_start] >> ay) & 1u) {  // (one address: wave-uniform)
-            n = layer;
-            break;
-        }
-        if (!__ballot(grew)) break;
-    }
-
-    // (d) the walk
-    uint64_t w0 = kRouteNone, w1 = kRouteNone;
-    if (n > 0) {
-        int r = rot, cx = cx0, y = ay, l = lock0;
-        const int m = n < ST_ROUTE_MAX ? n : ST_ROUTE_MAX;
-        for (int i = 0; i < m; ++i) {
-            const int d = n - i;  // D(r, cx, y, l); below 2^16, the number of states
-            int r2 = r, cx2 = cx, y2 = y, l2 = l;
-            bool ok = false;
-            if (lane < 7) {  // action `lane` on the state (:245-262)
-                if (lane == 0) cx2 -= is_free(r2, cx2 - 1, y2) ? 1 : 0;
-                else if (lane == 1) cx2 += is_free(r2, cx2 + 1, y2) ? 1 : 0;
-                else if (lane == 2) y2 += __builtin_ctz(~(y2 < 31 ? F[r2 * per + cx2] >> (y2 + 1) : 0u));
-                else if (lane == 3) y2 += is_free(r2, cx2, y2 + 1) ? 1 : 0;
-                else if (lane == 4) r2 = is_free((r2 + 1) & 3, cx2, y2) ? (r2 + 1) & 3 : r2;
-                else if (lane == 5) r2 = is_free((r2 + 3) & 3, cx2, y2) ? (r2 + 3) & 3 : r2;
-                if (is_free(r2, cx2, y2 + 1)) {
-                    ++y2;
-                    l2 = sreset ? 0 : l2;
-                }
-                const int s1 = r2 * per + cx2;
-                bool locked = false;
-                if (!is_free(r2, cx2, y2 + 1)) {
-                    l2 = l2 + 1 == NP ? 0 : l2 + 1;
-                    locked = l2 == 0;
-                }
-                if (locked) ok = n - i == 1 && s1 == tgt && ((tland >> y2) & 1u);
-                else
-                    ok = n - i > 1 && ((B[l2 * S + s1] >> y2) & 1u) &&
-                         D[((l2 * S + s1) << 5) + y2] == (uint16_t)(d - 1);
-            }
-            const uint64_t won = __ballot(ok);
-            if (won == 0) break;  // (D(x) = d has a successor at d - 1: not taken)
-            const int a = __builtin_ctzll(won);
-            const int nx = __shfl(r2 | cx2 << 2 | y2 << 10 | l2 << 16, a);
-            r = nx & 3;
-            cx = (nx >> 2) & 255;
-            y = (nx >> 10) & 63;
-            l = nx >> 16;
-            const uint64_t fld = (uint64_t)(7 - a) << (3 * (i % 21));  // 7 -> a: clear the bits a lacks
-            if (i < 21) w0 ^= fld;
-            else w1 ^= fld;
-        }
-    }
-    if (lane == 0) {
-        io.route[e] = w0;
-        io.route[p.n + e] = w1;
-        if (io.steps) io.steps[e] = n;
-        if (io.rem) io.rem[e] = n < ST_ROUTE_MAX ? n : ST_ROUTE_MAX;
-    }
-}
-
-#ifdef ST_ROUTES_TU
-// st_play_routed's pop: one lane per env takes its route's next action (2
-// without a route) and counts the piece with a route's last one.
-__global__ __launch_bounds__(256) void k_route_pop(int64_t n, const uint64_t *__restrict__ route,
-                                                   const int32_t *__restrict__ steps, int32_t *__restrict__ rem,
-                                                   uint8_t *__restrict__ act, int32_t *__restrict__ pieces) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n) return;
-    const int32_t r = rem[e];
-    uint32_t a = 2u;
-    if (r > 0) {
-        const int32_t st = steps[e];
-        const int i = (st < ST_ROUTE_MAX ? st : ST_ROUTE_MAX) - r;
-        a = (uint32_t)(route[(int64_t)(i / 21) * n + e] >> (3 * (i % 21))) & 7u;
-        rem[e] = r - 1;
-        if (pieces && r == 1 && st <= ST_ROUTE_MAX) pieces[e] += 1;
-    }
-    act[e] = (uint8_t)a;
-}
-#endif  // ST_ROUTES_TU (k_route_pop)
-#endif  // ST_ROUTES_TU || ST_LOCKS_TU
-
-#ifdef ST_LOCKS_TU
-// ---------------------------------------------------------------- lock positions
-// st_lock_set / st_afterstates_at / st_routes_at / st_policy_locks /
-// st_play_locks: every (rot, x, y) the live piece can be locked at
-// (simpletetris.h, "Lock positions"), a tuck under an overhang included -- the
-// placements k_reachable's search walks through and then masks away with the
-// landing bit.  One wave per env, a lane per slot, whole-row bit sets, as
-// k_reachable / k_routes:
-//  forward   k_reachable<false, false>'s layers; the last plane's grounded rows
-//            that are free (grounded & F[s]: a start that collides and locks
-//            where it stands is none) are ORed into the slot's lock word
-//            K[s] on every layer.  The start's own layer needs nothing of its
-//            own: the start state sits in the set of its plane, idle keeps it
-//            there, and layer 1 grounds and locks it like any other.
-//  choice    a lane walks the bits of its slots' lock words in ascending
-//            pos = slot * 32 + y, evaluates each with eval_at_set (the rows of
-//            eval_slot_set with the piece set at (x, y)), scores it with
-//            lin_score and keeps its first maximum; the wave's choice is
-//            k_routes's pair of wave_reduces on (score, lowest pos).
-//  backward, walk   k_routes's (c) and (d) with "the target's landing" read
-//            as bit y of slot s.
-// LDS: k_routes's layout (route_lds_bytes), R holding the lock words;
-// k_lock_set needs no D.
-
-// eval_slot_set with the anchor row given: the piece at (x, y) is evaluable
-// iff it is collision-free there and occupied a row lower (s in [0, S),
-// 0 <= y < H: the caller checks).  It restates eval_slot_set for the reason
-// eval_slot_set restates eval_slot (a row parameter on either moves the
-// existing kernels' instructions) and must follow it change for change; the
-// tests hold it to st_afterstates_set's rows bit for bit at every landing.
-template <int SET, class ColOut>
-__device__ __forceinline__ bool eval_at_set(const uint32_t *C, int W, int H, uint32_t flags, int id, int s, int y,
-                                            int32_t old_holes, int32_t old_height, int32_t (&f)[feat_rows(SET)],
-                                            ColOut col_out) {
-    constexpr bool EXT = SET == ST_FEATS_BCTS;
-    const uint32_t hmask = (1u << H) - 1u, floorb = ~hmask;
-    const int per = W + 6;
-    const int r = (s >= per) + (s >= 2 * per) + (s >= 3 * per), x = s - r * per - 3;
-    const uint32_t m = c_tab_m[id * 4 + r], g = c_tab_g[id * 4 + r];
-    const int x0 = box_x0(g, x);
-    uint32_t v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = C[x0 + j];
-    const bool valid = !collides_v(m, y, v) && collides_v(m, y + 1, v);
-    bool above = false;
-    uint32_t pb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t byte = (m >> (8 * j)) & 0xFFu;
-        above = above || (byte != 0u && y + __builtin_ctz(byte) - 3 < 0);  // (a box column without cells)
-        pb[j] = pc_bits(m, j, y) & hmask;
-    }
-    // the board with the piece: column c gets the bits of the box column at c
-    uint32_t andv = hmask;
-    for (int c = 0; c < W; ++c) {
-        uint32_t w = C[c];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
-        andv &= w;
-    }
-    const int32_t ncl = __builtin_popcount(andv);
-    int32_t holes = 0, agg = 0, bump = 0, hprev = 0;
-    uint32_t orv = 0;
-    ExtAcc<EXT> x_;
-    if constexpr (EXT) x_.w1 = x_.w2 = hmask;  // the left wall
-    for (int c = 0; c < W; ++c) {
-        uint32_t w = C[c] & hmask;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w |= x0 + j == c ? pb[j] : 0u;
-        if (andv) w = compact(w, andv);
-        if constexpr (EXT) {
-            x_.rtr += __builtin_popcount(x_.w1 ^ w);
-            const uint32_t wf = w | (1u << H);  // the floor counts as filled
-            x_.ctr += __builtin_popcount((wf ^ (wf >> 1)) & hmask);
-            if (c) x_.wells += well_sum(~x_.w1 & x_.w2 & w & hmask);  // column c - 1
-            const uint32_t top = w & (0u - w);                // the column's topmost cell (0: none)
-            uint32_t hl = ~w & hmask & ~(top | (top - 1u));   // its holes: empty, below the top
-            x_.hole_or |= hl;
-            while (hl) {
-                x_.hdepth += __builtin_popcount(w & ((hl & (0u - hl)) - 1u));  // the cells above this hole
-                hl &= hl - 1u;
-            }
-            x_.w2 = x_.w1;
-            x_.w1 = w;
-        }
-        const int32_t h = H - (int32_t)__builtin_ctz(w | floorb);  // the column's height
-        holes += h - __builtin_popcount(w);
-        agg += h;
-        bump += c ? (h > hprev ? h - hprev : hprev - h) : 0;
-        hprev = h;
-        orv |= w;
-        col_out(c, w, valid);
-    }
-    int32_t rew = (flags & ST_REWARD_STEP) ? 1 : 0;  // :256
-    int32_t score = 0, lines = 0, nholes = 0, height = 0, deaths = 0;
-    lock_score<false>(flags, ncl, orv, [&] { return holes; }, old_holes, old_height, rew, score, lines, nholes, height,
-                      deaths);
-    f[ST_AFTER_VALID] = 1;
-    f[ST_AFTER_Y] = y;
-    f[ST_AFTER_LINES] = ncl;
-    f[ST_AFTER_HOLES] = holes;
-    f[ST_AFTER_HEIGHT] = orv ? H - (int32_t)__builtin_ctz(orv) : 0;
-    f[ST_AFTER_ROWS] = __builtin_popcount(orv);
-    f[ST_AFTER_ABOVE] = above ? 1 : 0;
-    f[ST_AFTER_DEAD] = (int32_t)(orv & 1u);
-    f[ST_AFTER_REWARD] = rew;
-    f[ST_AFTER_AGG_HEIGHT] = agg;
-    f[ST_AFTER_BUMPINESS] = bump;
-    if constexpr (EXT) {
-        x_.rtr += __builtin_popcount(x_.w1 ^ hmask);    // the last column against the right wall
-        x_.wells += well_sum(~x_.w1 & x_.w2 & hmask);   // column W - 1 (W >= 4: w2 is column W - 2)
-        // the rows the piece spans, unclipped: bit dy + 3 of a box byte is row y + dy
-        const uint32_t span = (m | m >> 8 | m >> 16 | m >> 24) & 0xFFu;
-        const int32_t ymin = y + (int32_t)__builtin_ctz(span) - 3, ymax = y + 28 - (int32_t)__builtin_clz(span);
-        int32_t gone = 0;  // cells of the piece, inside the board, in a row that was cleared
-#pragma unroll
-        for (int j = 0; j < 4; ++j) gone += __builtin_popcount(pb[j] & andv);
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_LANDING2] = 2 * H - 1 - (ymin + ymax);
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_ERODED] = ncl * gone;
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_ROW_TRANS] = x_.rtr;
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_COL_TRANS] = x_.ctr;
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_WELLS] = x_.wells;
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_HOLE_DEPTH] = x_.hdepth;
-        f[ST_AFTER_NFEAT + ST_AFTER_EXT_HOLE_ROWS] = __builtin_popcount(x_.hole_or);
-    }
-    return valid;
-}
-
-// The env's piece word as k_reachable reads it.
-struct LockStart {
-    int id, rot, cx0, ay, lock0;
-    bool ok;  // inside the lane grid and the row word (k_reachable: any other start reaches no slot)
-};
-__device__ __forceinline__ LockStart lock_start(uint32_t pw, int per, int NP) {
-    LockStart st;
-    const uint32_t pid = pw & 7u;
-    st.id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
-    st.rot = (int)((pw >> 3) & 3u);
-    st.cx0 = (int)((pw >> 5) & 63u) + 3;
-    st.ay = (int)((pw >> 11) & 63u);
-    st.lock0 = (int)(pw >> 17) < NP ? (int)(pw >> 17) : NP - 1;  // (as k_reachable reads it)
-    st.ok = st.cx0 < per && st.ay < 32;
-    return st;
-}
-
-// The forward layers: K[s] |= the rows the piece locks at in slot s.  F is
-// filled, K and both copies of A are zero, and the wave has synchronised.
-__device__ __forceinline__ void lock_forward(const uint32_t *F, uint32_t *K, uint32_t *A, int S, int per, int H, int NP,
-                                             bool sreset, const LockStart &st, int lane) {
-    const int setw = NP * S;
-    if (st.ok && lane == 0) A[st.lock0 * S + st.rot * per + st.cx0] = 1u << st.ay;
-    wave_sync();
-    int cur = 0;
-    const int max_fwd = st.ok ? 4 * per * H * NP : 0;
-    for (int layer = 1; layer <= max_fwd; ++layer) {
-        const uint32_t *const In = A + cur * setw;
-        uint32_t *const Out = A + (cur ^ 1) * setw;
-        bool grew = false;
-        for (int s = lane; s < S; s += kWave) {
-            const uint32_t f = F[s], fd = f >> 1;
-            const int sl = s > 0 ? s - 1 : 0, sr = s < S - 1 ? s + 1 : s;
-            const int su = s + per < S ? s + per : s + per - S, sd = s >= per ? s - per : s - per + S;
-            uint32_t mvall = 0;
-            for (int l = 0; l < NP; ++l) {
-                const uint32_t *const I = In + l * S;
-                const uint32_t a = I[s];
-                const uint32_t nb = I[sl] | I[sr] | I[su] | I[sd];
-                const uint32_t pos = a | ((nb | (a << 1)) & f) | (reach_fall(a, f) & ~fd);
-                Out[l * S + s] = pos;
-                mvall |= (pos << 1) & f;
-            }
-            uint32_t grounded = 0;
-            for (int l = 0; l < NP; ++l) {
-                const uint32_t pos = Out[l * S + s];
-                const uint32_t moved = sreset ? (l == 0 ? mvall : 0u) : (pos << 1) & f;
-                const uint32_t g = (pos & ~fd) | moved;
-                const uint32_t old = In[l * S + s];
-                const uint32_t nw = old | (g & fd) | grounded;
-                Out[l * S + s] = nw;
-                grew = grew || nw != old;
-                grounded = g & ~fd;
-            }
-            K[s] |= grounded & f;  // the counter wraps: the piece locks, collision-free
-        }
-        wave_sync();
-        cur ^= 1;
-        if (!__ballot(grew)) break;
-    }
-}
-
-__device__ __forceinline__ int wave_sum(int x) {  // over all 64 lanes, in every lane
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) x += __shfl_xor(x, d);
-    return x;
-}
-
-// st_lock_set: rows uint32 [n][S], pos int32 [n][cap], count int32 [n], any null
-__global__ __launch_bounds__(kWave) void k_lock_set(KParams p, uint32_t *__restrict__ rows, int32_t *__restrict__ pos,
-                                                    int64_t cap, int32_t *__restrict__ count) {
-    extern __shared__ uint32_t lock_lds[];
-    const int lane = threadIdx.x;
-    const int64_t e = blockIdx.x;  // the grid is p.n waves
-    const int W = p.W, H = p.H, per = W + 6, S = 4 * per;
-    const int NP = p.lock_mod;  // (the host checked L <= ST_REACH_MAX_LOCK)
-    uint32_t *const C = lock_lds;        // column words
-    uint32_t *const F = C + kAfterCols;  // [S] free rows
-    uint32_t *const K = F + S;           // [S] lock rows
-    uint32_t *const A = K + S;           // [2][NP][S]
-    stage_env_columns(C, p, e, lane);
-    const LockStart st = lock_start(p.piece[e], per, NP);
-    wave_sync();
-    for (int s = lane; s < S; s += kWave) {
-        F[s] = reach_free(C + kAfterP, W, st.id, s);
-        K[s] = 0u;
-        for (int k = 0; k < 2 * NP; ++k) A[k * S + s] = 0u;
-    }
-    wave_sync();
-    lock_forward(F, K, A, S, per, H, NP, (p.flags & ST_STEP_RESET) != 0u, st, lane);
-
-    // the list: a lane's count, the wave's prefix sum, a walk over the lane's bits -- pass by pass, since
-    // the slots of a pass all come before the next pass's
-    int32_t base = 0;
-    for (int s0 = 0; s0 < S; s0 += kWave) {
-        const int s = s0 + lane;
-        uint32_t w = s < S ? K[s] : 0u;
-        if (rows && s < S) rows[(size_t)e * S + s] = w;
-        const int c = __builtin_popcount(w);
-        int x = c;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int t = __shfl_up(x, d);
-            x += lane >= d ? t : 0;
-        }
-        int64_t i = base + x - c;
-        if (pos) {
-            while (w) {
-                if (i < cap) pos[(size_t)e * (size_t)cap + (size_t)i] = s * 32 + __builtin_ctz(w);
-                ++i;
-                w &= w - 1u;
-            }
-        }
-        base += __shfl(x, kWave - 1);
-    }
-    if (pos)
-        for (int64_t i = base + lane; i < cap; i += kWave) pos[(size_t)e * (size_t)cap + (size_t)i] = -1;
-    if (count && lane == 0) count[e] = base;
-}
-
-// st_afterstates_at: pos int32 [n][cap] (any values) -> feat int32 [n][rows][cap], boards uint32 [n][W][cap] or
-// null; a lane per entry, ceil(cap / 64) passes; a non-evaluable entry stores zeros
-template <int SET>
-__global__ __launch_bounds__(kWave) void k_afterstates_at(KParams p, const int32_t *__restrict__ pos, int64_t cap,
-                                                          int32_t *__restrict__ feat, uint32_t *__restrict__ boards) {
-    constexpr int NF = feat_rows(SET);
-    __shared__ uint32_t L[kAfterCols];
-    const int lane = threadIdx.x;
-    const int64_t e = blockIdx.x;  // the grid is p.n waves
-    const int64_t sd = p.stride;
-    const int W = p.W, H = p.H;
-    const int S = 4 * (W + 6);
-    stage_env_columns(L, p, e, lane);
-    const uint32_t pid = p.piece[e] & 7u;
-    const int id = (int)(pid < 7u ? pid : 6u);  // (a host-written id 7 stays inside the table)
-    const int32_t old_holes = p.stats[ST_STAT_HOLES * sd + e];
-    const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd + e];
-    wave_sync();
-    const size_t ucap = (size_t)cap;
-    const size_t fbase = (size_t)e * NF * ucap, bbase = (size_t)e * W * ucap;
-    for (int64_t i0 = 0; i0 < cap; i0 += kWave) {
-        const int64_t i = i0 + lane;
-        const bool live = i < cap;
-        const int32_t q = live ? pos[(size_t)e * ucap + (size_t)i] : -1;
-        const bool dec = q >= 0 && (q >> 5) < S && (q & 31) < H;  // decodes to a slot and a row of the board
-        const int s = dec ? q >> 5 : S - 1, y = dec ? q & 31 : 0;  // (others compute something, store zeros)
-        int32_t f[NF];
-        const bool valid = eval_at_set<SET>(L + kAfterP, W, H, p.flags, id, s, y, old_holes, old_height, f,
-                                            [&](int c, uint32_t w, bool ok) {
-                                                if (boards && live)
-                                                    boards[bbase + (size_t)c * ucap + (size_t)i] = ok && dec ? w : 0u;
-                                            });
-        if (live) {
-#pragma unroll
-            for (int row = 0; row < NF; ++row)
-                feat[fbase + (size_t)row * ucap + (size_t)i] = valid && dec ? f[row] : 0;
-        }
-    }
-}
-
-struct LockIO {
-    const int32_t *pos_in;  // st_routes_at: the targets int32 [n]
-    const uint8_t *need;    // uint8 [n] or null: every env
-    int32_t *rem;           // st_play_locks: an env is needed iff rem[e] == 0, and gets min(steps, ST_ROUTE_MAX)
-    const float *wts;       // the planner: float [n_w][rows]
-    int64_t n_w;
-    int32_t *pos;           // the planner: the chosen position int32 [n]
-    uint64_t *route;        // uint64 [ST_ROUTE_WORDS][n]; the planner: or null (no backward search, no walk)
-    int32_t *steps;         // int32 [n] or null
-    float *scores;          // the planner: float [n] or null
-    int32_t *best;          // the planner: int32 [rows][n] or null
-    int32_t *count;         // the planner: int32 [n] or null
-};
-
-// SET: a feature set -- the planner (st_policy_locks / st_play_locks); -1 -- st_routes_at for pos_in[e]
-template <int SET>
-__global__ __launch_bounds__(kWave) void k_locks(KParams p, LockIO io) {
-    extern __shared__ uint32_t lock_lds[];
-    const int lane = threadIdx.x;
-    const int64_t e = blockIdx.x;  // the grid is p.n waves
-    if (io.rem ? io.rem[e] != 0 : (io.need != nullptr && io.need[e] == 0)) return;  // (wave-uniform)
-    const int W = p.W, H = p.H, per = W + 6, S = 4 * per;
-    const int NP = p.lock_mod;  // (the host checked L <= ST_REACH_MAX_LOCK)
-    const bool sreset = (p.flags & ST_STEP_RESET) != 0u;
-    uint32_t *const C = lock_lds;        // column words
-    uint32_t *const F = C + kAfterCols;  // [S] free rows
-    uint32_t *const K = F + S;           // [S] lock rows
-    uint32_t *const A = K + S;           // [2][NP][S]
-    uint16_t *const D = reinterpret_cast<uint16_t *>(A + 2 * NP * S);  // [NP][S][32]
-    const int setw = NP * S;
-
-    stage_env_columns(C, p, e, lane);
-    const LockStart st = lock_start(p.piece[e], per, NP);
-    const int id = st.id, rot = st.rot, cx0 = st.cx0, ay = st.ay, lock0 = st.lock0;
-    wave_sync();
-    for (int s = lane; s < S; s += kWave) {
-        F[s] = reach_free(C + kAfterP, W, id, s);
-        K[s] = 0u;
-        for (int k = 0; k < 2 * NP; ++k) A[k * S + s] = 0u;
-    }
-    wave_sync();
-    auto is_free = [&](int r, int cx, int y) -> bool {
-        return cx >= 0 && cx < per && y < 32 && ((F[r * per + cx] >> y) & 1u);
-    };
-
-    int tgt = -1, ty = 0;  // the target: slot and row
-    if constexpr (SET >= 0) {
-        lock_forward(F, K, A, S, per, H, NP, sreset, st, lane);
-
-        constexpr int NF = feat_rows(SET);
-        const int64_t sd_ = p.stride;
-        const int32_t old_holes = p.stats[ST_STAT_HOLES * sd_ + e];
-        const int32_t old_height = p.stats[ST_STAT_PIECE_HEIGHT * sd_ + e];
-        const uint32_t wrow = io.n_w > e ? (uint32_t)e : (uint32_t)e % (uint32_t)io.n_w;
-        float w[NF];
-#pragma unroll
-        for (int r = 0; r < NF; ++r) w[r] = io.wts[(size_t)wrow * NF + r];
-        int32_t bpos = -1, nlock = 0;
-        float bscore = 0.0f;
-        int32_t bf[NF];
-#pragma unroll
-        for (int r = 0; r < NF; ++r) bf[r] = 0;
-        for (int s = lane; s < S; s += kWave) {
-            uint32_t k = K[s];
-            nlock += __builtin_popcount(k);
-            while (k) {  // (mostly one row, sometimes two or three)
-                const int y = __builtin_ctz(k);
-                k &= k - 1u;
-                int32_t f[NF];
-                const bool valid = eval_at_set<SET>(C + kAfterP, W, H, p.flags, id, s, y, old_holes, old_height, f,
-                                                    [](int, uint32_t, bool) {});
-                const float sc = lin_score(w, f);
-                if (valid && (bpos < 0 || sc > bscore)) {  // (a lane's positions ascend: the first maximum stays)
-                    bpos = s * 32 + y;
-                    bscore = sc;
-#pragma unroll
-                    for (int r = 0; r < NF; ++r) bf[r] = f[r];
-                }
-            }
-        }
-        const bool has = bpos >= 0;
-        const float top =
-            __int_as_float(wave_reduce(__float_as_int(has ? bscore : -__builtin_inff()), [](int a, int b) {
-                return __float_as_int(__builtin_fmaxf(__int_as_float(a), __int_as_float(b)));
-            }));
-        bool tied = has && bscore == top;
-        if (__ballot(tied) == 0) tied = has;  // (a NaN score equals nothing: every candidate counts)
-        const int32_t win = wave_reduce(tied ? bpos : INT32_MAX, [](int a, int b) { return a < b ? a : b; });
-        const bool none = win == INT32_MAX;
-        if (none ? lane == 0 : tied && bpos == win) {
-            io.pos[e] = none ? -1 : win;
-            if (io.scores) io.scores[e] = none ? 0.0f : bscore;
-            if (io.best) {
-#pragma unroll
-                for (int r = 0; r < NF; ++r) io.best[(size_t)r * p.n + e] = none ? 0 : bf[r];
-            }
-        }
-        if (io.count) {
-            const int total = wave_sum(nlock);
-            if (lane == 0) io.count[e] = total;
-        }
-        if (io.route == nullptr) return;  // (wave-uniform) the choice alone: steps is not written either
-        tgt = none ? -1 : win >> 5;
-        ty = none ? 0 : win & 31;
-        wave_sync();
-        for (int s = lane; s < S; s += kWave)
-            for (int k = 0; k < NP; ++k) A[k * S + s] = 0u;  // B
-        wave_sync();
-    } else {
-        const int32_t q = io.pos_in[e];
-        if (q >= 0 && (q >> 5) < S && (q & 31) < H) {
-            tgt = q >> 5;
-            ty = q & 31;
-        }
-    }
-
-    // the backward layers (k_routes (c)): the target is collision-free and grounded at row ty, or not served
-    uint32_t *const B = A, *const Q = A + setw;
-    const int s_start = rot * per + (cx0 < per ? cx0 : 0);
-    const uint32_t ftgt = tgt >= 0 ? F[tgt] : 0u;
-    const bool search = st.ok && ((ftgt >> ty) & 1u) && !((ftgt >> (ty + 1)) & 1u);  // (ty + 1 <= H <= 28)
-    const uint32_t tland = search ? 1u << ty : 0u;
-    const int max_layer = search ? 4 * per * H * NP : 0;
-    int n = 0;  // steps: the layer at which the start state joined
-    for (int layer = 1; layer <= max_layer; ++layer) {
-        for (int s = lane; s < S; s += kWave) {
-            const uint32_t fd = F[s] >> 1, tb = s == tgt ? tland : 0u;
-            uint32_t E[kRoutePlanes];
-#pragma unroll
-            for (int l = 0; l < kRoutePlanes; ++l)
-                if (l < NP) E[l] = (fd & B[l * S + s]) | (~fd & (l + 1 == NP ? tb : B[(l + 1 < NP ? l + 1 : l) * S + s]));
-#pragma unroll
-            for (int l = 0; l < kRoutePlanes; ++l)
-                if (l < NP) Q[l * S + s] = (~fd & E[l]) | (fd & ((sreset ? E[0] : E[l]) >> 1));
-        }
-        wave_sync();
-        bool grew = false;
-        for (int s = lane; s < S; s += kWave) {
-            const uint32_t fd = F[s] >> 1;
-            const int sl = s > 0 ? s - 1 : 0, sr = s < S - 1 ? s + 1 : s;
-            const int su = s + per < S ? s + per : s + per - S, sd = s >= per ? s - per : s - per + S;
-            const uint32_t fl = F[sl], fr = F[sr], fu = F[su], fdn = F[sd];
-            for (int l = 0; l < NP; ++l) {
-                const uint32_t *const Ql = Q + l * S;
-                const uint32_t q = Ql[s];
-                const uint32_t pre = q | (fl & Ql[sl]) | (fr & Ql[sr]) | (fu & Ql[su]) | (fdn & Ql[sd]) |
-                                     (fd & (q >> 1)) | route_rise(q & ~fd, fd);
-                const uint32_t old = B[l * S + s];
-                uint32_t nw = pre & ~old;
-                if (nw) {
-                    B[l * S + s] = old | nw;
-                    grew = true;
-                    do {
-                        D[((l * S + s) << 5) + __builtin_ctz(nw)] = (uint16_t)layer;
-                        nw &= nw - 1u;
-                    } while (nw);
-                }
-            }
-        }
-        wave_sync();
-        if ((B[lock0 * S + s_start] >> ay) & 1u) {  // (one address: wave-uniform)
-            n = layer;
-            break;
-        }
-        if (!__ballot(grew)) break;
-    }
-
-    // the walk (k_routes (d))
-    uint64_t w0 = kRouteNone, w1 = kRouteNone;
-    if (n > 0) {
-        int r = rot, cx = cx0, y = ay, l = lock0;
-        const int m = n < ST_ROUTE_MAX ? n : ST_ROUTE_MAX;
-        for (int i = 0; i < m; ++i) {
-            const int d = n - i;  // D(r, cx, y, l); below 2^16, the number of states
-            int r2 = r, cx2 = cx, y2 = y, l2 = l;
-            bool ok = false;
-            if (lane < 7) {  // action `lane` on the state (:245-262)
-                if (lane == 0) cx2 -= is_free(r2, cx2 - 1, y2) ? 1 : 0;
-                else if (lane == 1) cx2 += is_free(r2, cx2 + 1, y2) ? 1 : 0;
-                else if (lane == 2) y2 += __builtin_ctz(~(y2 < 31 ? F[r2 * per + cx2] >> (y2 + 1) : 0u));
-                else if (lane == 3) y2 += is_free(r2, cx2, y2 + 1) ? 1 : 0;
-                else if (lane == 4) r2 = is_free((r2 + 1) & 3, cx2, y2) ? (r2 + 1) & 3 : r2;
-                else if (lane == 5) r2 = is_free((r2 + 3) & 3, cx2, y2) ? (r2 + 3) & 3 : r2;
-                if (is_free(r2, cx2, y2 + 1)) {
-                    ++y2;
-                    l2 = sreset ? 0 : l2;
-                }
-                const int s1 = r2 * per + cx2;
-                bool locked = false;
-                if (!is_free(r2, cx2, y2 + 1)) {
-                    l2 = l2 + 1 == NP ? 0 : l2 + 1;
-                    locked = l2 == 0;
-                }
-                if (locked) ok = n - i == 1 && s1 == tgt && ((tland >> y2) & 1u);
-                else
-                    ok = n - i > 1 && ((B[l2 * S + s1] >> y2) & 1u) &&
-                         D[((l2 * S + s1) << 5) + y2] == (uint16_t)(d - 1);
-            }
-            const uint64_t won = __ballot(ok);
-            if (won == 0) break;  // (D(x) = d has a successor at d - 1: not taken)
-            const int a = __builtin_ctzll(won);
-            const int nx = __shfl(r2 | cx2 << 2 | y2 << 10 | l2 << 16, a);
-            r = nx & 3;
-            cx = (nx >> 2) & 255;
-            y = (nx >> 10) & 63;
-            l = nx >> 16;
-            const uint64_t fld = (uint64_t)(7 - a) << (3 * (i % 21));  // 7 -> a: clear the bits a lacks
-            if (i < 21) w0 ^= fld;
-            else w1 ^= fld;
-        }
-    }
-    if (lane == 0) {
-        io.route[e] = w0;
-        io.route[p.n + e] = w1;
-        if (io.steps) io.steps[e] = n;
-        if (io.rem) io.rem[e] = n < ST_ROUTE_MAX ? n : ST_ROUTE_MAX;
-    }
-}
-#endif  // ST_LOCKS_TU
-
-#ifdef ST_FORK_TU
-// ---------------------------------------------------------------- fork
-// st_fork: env e of p (dst) takes the state of env index[e] of f (src) --
-// copy.deepcopy of the TetrisEngine with random.getstate(), or with KEEP
-// (ST_FORK_KEEP_RNG) the engine alone while the env keeps its own stream.
-// One workgroup of WAVES waves per 64 dst envs.  Every wave reads the 64
-// indices and mask bytes (an env is WRITTEN iff it is real, masked in and its
-// index lies in [0, f.n): nothing else is ever read or stored, so padding envs
-// are neither sources nor targets).  Wave 0, lane = env, copies the W board
-// rows and the counter rows: the stores into dst's SoA rows are coalesced, the
-// loads gathers by index (one address for a broadcast).  Deep copy: the written
-// lanes' MT rows -- kMtPitch words: both generation buffers and the pad, so the
-// progress bits, a pending preview and its consumed-word count in the index
-// word stay true of them -- are then copied one env at a time, 16 B per lane
-// (kMtPitch * 4 = 316 * 16 B, every row base 16-B aligned), the written lanes
-// dealt round robin to the waves, each wave loading its next row before it
-// stores the present one.  (WAVES = 1 is the library's grid: four waves per
-// 64 envs measured no faster, DESIGN.md "Fork".)  KEEP: no MT row moves; the written envs are put into
-// CPython's form first (mt_sync_lanes: a preview they hold was drawn under the
-// old shape counts, tetris_env.py:183-191, so its words go back), which wave 0
-// does alone.
-struct ForkSrc {
-    const uint32_t *board;  // [W][stride]
-    const int32_t *stats;   // [ST_NSTAT][stride]
-    const uint32_t *mt;     // [stride][kMtPitch]
-    int64_t n, stride;
-    const int32_t *index;   // [p.n] or null: e
-    const uint8_t *mask;    // [p.n] or null: every env
-    int32_t same;           // f is p's own context: a deep copy of an env onto itself is skipped
-};
-constexpr int kMtRowQ = (int)(kMtPitch / 4);        // 16-B words of an MT row
-constexpr int kForkQ = (kMtRowQ + kWave - 1) / kWave;  // per lane
-static_assert(kMtPitch % 4 == 0, "MT rows are copied in 16-B accesses");
-
-template <int WAVES, bool KEEP>
-__global__ __launch_bounds__(WAVES *kWave) void k_fork(KParams p, ForkSrc f) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-    const int64_t e0 = (int64_t)blockIdx.x * kWave;
-    const int64_t e = e0 + lane;
-    const int64_t sd = p.stride, ss = f.stride;
-    bool wr = e < p.n && (f.mask == nullptr || f.mask[e] != 0);
-    int64_t s64 = e;
-    if (e < p.n && f.index) s64 = f.index[e];
-    wr = wr && s64 >= 0 && s64 < f.n;
-    if (!KEEP && f.same && s64 == e) wr = false;
-    const int s = wr ? (int)s64 : 0;  // (f.n <= 2^24)
-
-    [[maybe_unused]] int idx = 0;
-    if constexpr (KEEP) {
-        const uint32_t r = wr ? (uint32_t)p.stats[(int64_t)ST_STAT_MT_INDEX * sd + e] : 0u;
-        idx = mt_sync_lanes(p.mt, e0, r, wr, lane);
-    }
-    if (wave == 0 && wr) {
-        int32_t t[ST_NSTAT];
-#pragma unroll
-        for (int r = 0; r < ST_NSTAT; ++r)
-            t[r] = KEEP && r == ST_STAT_MT_INDEX ? idx : f.stats[(int64_t)r * ss + s];
-        for (int x0 = 0; x0 < p.W; x0 += 8) {
-            uint32_t b[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) b[j] = x0 + j < p.W ? f.board[(int64_t)(x0 + j) * ss + s] : 0u;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (x0 + j < p.W) p.board[(int64_t)(x0 + j) * sd + e] = b[j];
-        }
-#pragma unroll
-        for (int r = 0; r < ST_NSTAT; ++r) p.stats[(int64_t)r * sd + e] = t[r];
-    }
-    if constexpr (!KEEP) {
-        uint64_t m = __ballot(wr);
-        int turn = 0;
-        auto next = [&]() -> int {  // the wave's next written lane, or -1 (wave-uniform)
-            while (m) {
-                const int l = (int)__builtin_ctzll(m);
-                m &= m - 1;
-                if (turn++ % WAVES == wave) return l;
-            }
-            return -1;
-        };
-        auto load = [&](int l, u32x4(&v)[kForkQ]) {
-            const u32x4 *g = reinterpret_cast<const u32x4 *>(f.mt + (int64_t)__builtin_amdgcn_readlane(s, l) * kMtPitch);
-#pragma unroll
-            for (int q = 0; q < kForkQ; ++q) {
-                const int i = lane + kWave * q;
-                if (i < kMtRowQ) v[q] = g[i];
-            }
-        };
-        u32x4 a[kForkQ] = {}, b[kForkQ] = {};
-        int l = next();
-        if (l >= 0) load(l, a);
-        while (l >= 0) {
-            const int ln = next();
-            if (ln >= 0) load(ln, b);
-            u32x4 *g = reinterpret_cast<u32x4 *>(p.mt + (e0 + l) * kMtPitch);
-#pragma unroll
-            for (int q = 0; q < kForkQ; ++q) {
-                const int i = lane + kWave * q;
-                if (i < kMtRowQ) g[i] = a[q];
-            }
-#pragma unroll
-            for (int q = 0; q < kForkQ; ++q) a[q] = b[q];
-            l = ln;
-        }
-    }
-}
-#endif  // ST_FORK_TU
 
 }  // namespace
-
-// k_step's arguments: the preloaded six, then the whole KParams
-#define ST_STEP_ARGS(p) (p).board, (p).stats, (p).actions, (p).mt, (p).stride, (p).n, (p)
-
-#ifdef ST_STEP_EXPORT_TU
-hipError_t launch_step_export(const KParams &p, int64_t env, uint32_t parts, uint32_t *out, hipStream_t s) {
-    const dim3 grid((unsigned)(p.stride / kWave)), block(2 * kWave);  // logic + draw wave
-#define ST_STEP_EXPORT_ARGS ST_STEP_ARGS(p), env, p.obs, p.reward, p.done, parts, out
-    if (p.W == 10 && p.H == 20) {
-        if (!(p.flags & kScoringFlags)) hipLaunchKernelGGL((k_step_export<10, 20, true>), grid, block, 0, s, ST_STEP_EXPORT_ARGS);
-        else hipLaunchKernelGGL((k_step_export<10, 20, false>), grid, block, 0, s, ST_STEP_EXPORT_ARGS);
-    } else {
-        hipLaunchKernelGGL((k_step_export<0, 0, false>), grid, block, 0, s, ST_STEP_EXPORT_ARGS);
-    }
-#undef ST_STEP_EXPORT_ARGS
-    return hipGetLastError();
-}
-#elif defined(ST_AFTERSTATES_TU)
-hipError_t launch_afterstates(const KParams &p, int32_t *feat, uint32_t *boards, hipStream_t s) {
-    hipLaunchKernelGGL(k_afterstates, dim3((unsigned)p.n), dim3(kWave), 0, s, p, feat, boards);  // one wave per env
-    return hipGetLastError();
-}
-
-hipError_t launch_placement_actions(const KParams &p, const int32_t *slots, uint8_t *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_placement_actions, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p, slots, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_place(const KParams &p, const int32_t *slots, uint8_t *placed, hipStream_t s) {
-    hipLaunchKernelGGL(k_place, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p, slots, placed);
-    return hipGetLastError();
-}
-
-hipError_t launch_policy_linear_commit(const KParams &p, const float *weights, int64_t n_w, hipStream_t s) {
-    constexpr int WV = ST_POLICY_WAVES;
-    hipLaunchKernelGGL((k_policy_linear<WV, true>), dim3((unsigned)((p.n + WV - 1) / WV)), dim3(WV * kWave), 0, s, p,
-                       weights, n_w, (int32_t *)nullptr, (uint8_t *)nullptr, (float *)nullptr, (int32_t *)nullptr);
-    return hipGetLastError();
-}
-
-hipError_t launch_policy_linear(const KParams &p, const float *weights, int64_t n_w, int32_t *slots, uint8_t *actions,
-                                float *scores, int32_t *best, hipStream_t s) {
-    constexpr int WV = ST_POLICY_WAVES;
-    hipLaunchKernelGGL((k_policy_linear<WV>), dim3((unsigned)((p.n + WV - 1) / WV)), dim3(WV * kWave), 0, s, p, weights,
-                       n_w, slots, actions, scores, best);
-    return hipGetLastError();
-}
-
-hipError_t launch_play_sum(const KParams &p, const int32_t *reward, const uint8_t *done, int rows, int64_t *acc_return,
-                           int32_t *acc_episodes, int32_t *out_reward, uint8_t *out_done, hipStream_t s) {
-    hipLaunchKernelGGL(k_play_sum, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, reward, done, rows, p.n,
-                       acc_return, acc_episodes, out_reward, out_done);
-    return hipGetLastError();
-}
-#elif defined(ST_FEATURES_TU)
-hipError_t launch_afterstates_set(const KParams &p, int set, int32_t *feat, uint32_t *boards, hipStream_t s) {
-    if (set != ST_FEATS_BCTS) return hipErrorInvalidValue;  // (the base set is launch_afterstates)
-    hipLaunchKernelGGL((k_afterstates_set<ST_FEATS_BCTS>), dim3((unsigned)p.n), dim3(kWave), 0, s, p, feat, boards);
-    return hipGetLastError();
-}
-
-hipError_t launch_policy_linear_set(const KParams &p, int set, bool commit, const float *weights, int64_t n_w,
-                                    const int32_t *allowed, int32_t *slots, uint8_t *actions, float *scores,
-                                    int32_t *best, hipStream_t s) {
-    constexpr int WV = ST_POLICY_WAVES;
-    const dim3 grid((unsigned)((p.n + WV - 1) / WV)), block(WV * kWave);
-#define ST_PL_ARGS p, weights, n_w, allowed, slots, actions, scores, best
-    if (set == ST_FEATS_BCTS && commit)
-        hipLaunchKernelGGL((k_policy_linear_set<WV, true, ST_FEATS_BCTS>), grid, block, 0, s, ST_PL_ARGS);
-    else if (set == ST_FEATS_BCTS)
-        hipLaunchKernelGGL((k_policy_linear_set<WV, false, ST_FEATS_BCTS>), grid, block, 0, s, ST_PL_ARGS);
-    else if (set == ST_FEATS_BASE && !commit)  // (the base set without a mask is launch_policy_linear)
-        hipLaunchKernelGGL((k_policy_linear_set<WV, false, ST_FEATS_BASE>), grid, block, 0, s, ST_PL_ARGS);
-    else
-        return hipErrorInvalidValue;
-#undef ST_PL_ARGS
-    return hipGetLastError();
-}
-#elif defined(ST_LOOKAHEAD_TU)
-hipError_t launch_next_piece(const KParams &p, uint8_t *next, hipStream_t s) {
-    hipLaunchKernelGGL(k_next_piece, dim3((unsigned)(p.stride / kWave)), dim3(kWave), 0, s, p, next);
-    return hipGetLastError();
-}
-
-hipError_t launch_policy_lookahead(const KParams &p, int set, bool commit, const float *weights1,
-                                   const float *weights2, int64_t n_w, float dead_value, const int32_t *allowed,
-                                   int32_t *slots, int32_t *slots2, uint8_t *actions, float *scores,
-                                   float *scores_all, int32_t *slots2_all, hipStream_t s) {
-    if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS) return hipErrorInvalidValue;
-    // the preview the second ply places: drawn here where it is missing
-    if (const hipError_t e = launch_next_piece(p, nullptr, s); e != hipSuccess) return e;
-    const dim3 grid((unsigned)p.n), block(kLaWaves * kWave);  // one workgroup per env
-    const size_t lds = sizeof(uint32_t) * (size_t)(4 * (p.W + 6)) * (size_t)la_pitch(p.W);
-#define ST_LA_ARGS p, weights1, weights2, n_w, dead_value, allowed, slots, slots2, actions, scores, scores_all, slots2_all
-    if (set == ST_FEATS_BCTS && commit)
-        hipLaunchKernelGGL((k_policy_lookahead<ST_FEATS_BCTS, true>), grid, block, lds, s, ST_LA_ARGS);
-    else if (set == ST_FEATS_BCTS)
-        hipLaunchKernelGGL((k_policy_lookahead<ST_FEATS_BCTS, false>), grid, block, lds, s, ST_LA_ARGS);
-    else if (commit)
-        hipLaunchKernelGGL((k_policy_lookahead<ST_FEATS_BASE, true>), grid, block, lds, s, ST_LA_ARGS);
-    else
-        hipLaunchKernelGGL((k_policy_lookahead<ST_FEATS_BASE, false>), grid, block, lds, s, ST_LA_ARGS);
-#undef ST_LA_ARGS
-    return hipGetLastError();
-}
-#elif defined(ST_EXPECT_TU)
-hipError_t launch_next_weights(const KParams &p, int32_t *m, hipStream_t s) {
-    hipLaunchKernelGGL(k_next_weights, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p, m);
-    return hipGetLastError();
-}
-
-hipError_t launch_policy_expect(const KParams &p, int set, bool commit, const float *weights1, const float *weights2,
-                                int64_t n_w, float dead_value, const int32_t *allowed, int32_t *slots,
-                                uint8_t *actions, float *scores, float *scores_all, float *tails, int32_t *slots2_all,
-                                hipStream_t s) {
-    if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)p.n), block(kLaWaves * kWave);  // one workgroup per env
-    const size_t lds = sizeof(uint32_t) * (size_t)(4 * (p.W + 6)) * (size_t)la_pitch(p.W);
-#define ST_EX_ARGS p, weights1, weights2, n_w, dead_value, allowed, slots, actions, scores, scores_all, tails, slots2_all
-    if (set == ST_FEATS_BCTS && commit)
-        hipLaunchKernelGGL((k_policy_expect<ST_FEATS_BCTS, true>), grid, block, lds, s, ST_EX_ARGS);
-    else if (set == ST_FEATS_BCTS)
-        hipLaunchKernelGGL((k_policy_expect<ST_FEATS_BCTS, false>), grid, block, lds, s, ST_EX_ARGS);
-    else if (commit)
-        hipLaunchKernelGGL((k_policy_expect<ST_FEATS_BASE, true>), grid, block, lds, s, ST_EX_ARGS);
-    else
-        hipLaunchKernelGGL((k_policy_expect<ST_FEATS_BASE, false>), grid, block, lds, s, ST_EX_ARGS);
-#undef ST_EX_ARGS
-    return hipGetLastError();
-}
-#elif defined(ST_REACHABLE_TU)
-// column words, free / target / result words, two copies of the sets
-static size_t reach_lds_bytes(const KParams &p, int tags) {
-    const int S = 4 * (p.W + 6);
-    return sizeof(uint32_t) * (size_t)(kAfterCols + 3 * S + 2 * tags * p.lock_mod * S);
-}
-
-hipError_t launch_reachable(const KParams &p, int32_t *steps, uint8_t *first, hipStream_t s) {
-    const dim3 grid((unsigned)p.n), block(kWave);  // one wave per env
-    if (first)
-        hipLaunchKernelGGL((k_reachable<true, false>), grid, block, reach_lds_bytes(p, 7), s, p,
-                           (const int32_t *)nullptr, steps, first);
-    else
-        hipLaunchKernelGGL((k_reachable<false, false>), grid, block, reach_lds_bytes(p, 1), s, p,
-                           (const int32_t *)nullptr, steps, first);
-    return hipGetLastError();
-}
-
-hipError_t launch_route_actions(const KParams &p, const int32_t *slots, uint8_t *actions, int32_t *steps,
-                                hipStream_t s) {
-    hipLaunchKernelGGL((k_reachable<true, true>), dim3((unsigned)p.n), dim3(kWave), reach_lds_bytes(p, 7), s, p, slots,
-                       steps, actions);
-    return hipGetLastError();
-}
-#elif defined(ST_ROUTES_TU)
-// column words, free / result words, two copies of the sets, one uint16 per piece state
-static size_t route_lds_bytes(const KParams &p) {
-    const size_t S = 4 * (size_t)(p.W + 6), NP = (size_t)p.lock_mod;
-    return sizeof(uint32_t) * (kAfterCols + 2 * S + 2 * NP * S) + sizeof(uint16_t) * NP * S * 32;
-}
-
-hipError_t launch_routes(const KParams &p, int set, const float *weights, int64_t n_w, const int32_t *slots_in,
-                         const uint8_t *need, int32_t *rem, int32_t *slots, uint64_t *route, int32_t *steps,
-                         float *scores, hipStream_t s) {
-    const dim3 grid((unsigned)p.n), block(kWave);  // one wave per env
-    const size_t lds = route_lds_bytes(p);
-    const RouteIO io{slots_in, need, rem, weights, n_w, slots, route, steps, scores};
-    if (set == ST_FEATS_BCTS) hipLaunchKernelGGL((k_routes<ST_FEATS_BCTS>), grid, block, lds, s, p, io);
-    else if (set == ST_FEATS_BASE) hipLaunchKernelGGL((k_routes<ST_FEATS_BASE>), grid, block, lds, s, p, io);
-    else if (set == -1) hipLaunchKernelGGL((k_routes<-1>), grid, block, lds, s, p, io);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-hipError_t launch_route_pop(const KParams &p, const uint64_t *route, const int32_t *steps, int32_t *rem, uint8_t *act,
-                            int32_t *pieces, hipStream_t s) {
-    hipLaunchKernelGGL(k_route_pop, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p.n, route, steps, rem, act,
-                       pieces);
-    return hipGetLastError();
-}
-#elif defined(ST_LOCKS_TU)
-// k_locks: route_lds_bytes's layout (R holds the lock words); k_lock_set: the same without D
-static size_t lock_lds_bytes(const KParams &p, bool dist) {
-    const size_t S = 4 * (size_t)(p.W + 6), NP = (size_t)p.lock_mod;
-    return sizeof(uint32_t) * (kAfterCols + 2 * S + 2 * NP * S) + (dist ? sizeof(uint16_t) * NP * S * 32 : 0);
-}
-
-hipError_t launch_lock_set(const KParams &p, uint32_t *rows, int32_t *pos, int64_t cap, int32_t *count, hipStream_t s) {
-    hipLaunchKernelGGL(k_lock_set, dim3((unsigned)p.n), dim3(kWave), lock_lds_bytes(p, false), s, p, rows, pos, cap,
-                       count);  // one wave per env
-    return hipGetLastError();
-}
-
-hipError_t launch_afterstates_at(const KParams &p, int set, const int32_t *pos, int64_t cap, int32_t *feat,
-                                 uint32_t *boards, hipStream_t s) {
-    const dim3 grid((unsigned)p.n), block(kWave);  // one wave per env
-    if (set == ST_FEATS_BCTS) hipLaunchKernelGGL((k_afterstates_at<ST_FEATS_BCTS>), grid, block, 0, s, p, pos, cap, feat, boards);
-    else if (set == ST_FEATS_BASE) hipLaunchKernelGGL((k_afterstates_at<ST_FEATS_BASE>), grid, block, 0, s, p, pos, cap, feat, boards);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-hipError_t launch_locks(const KParams &p, int set, const float *weights, int64_t n_w, const int32_t *pos_in,
-                        const uint8_t *need, int32_t *rem, int32_t *pos, uint64_t *route, int32_t *steps,
-                        float *scores, int32_t *best, int32_t *count, hipStream_t s) {
-    const dim3 grid((unsigned)p.n), block(kWave);  // one wave per env
-    const size_t lds = lock_lds_bytes(p, true);
-    const LockIO io{pos_in, need, rem, weights, n_w, pos, route, steps, scores, best, count};
-    if (set == ST_FEATS_BCTS) hipLaunchKernelGGL((k_locks<ST_FEATS_BCTS>), grid, block, lds, s, p, io);
-    else if (set == ST_FEATS_BASE) hipLaunchKernelGGL((k_locks<ST_FEATS_BASE>), grid, block, lds, s, p, io);
-    else if (set == -1) hipLaunchKernelGGL((k_locks<-1>), grid, block, lds, s, p, io);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-#elif defined(ST_FORK_TU)
-hipError_t launch_fork(const KParams &dst, const KParams &src, const int32_t *index, const uint8_t *mask, bool keep_rng,
-                       int waves, hipStream_t s) {
-    const ForkSrc f{src.board, src.stats, src.mt, src.n, src.stride, index, mask, dst.stats == src.stats};
-    const dim3 grid((unsigned)(dst.stride / kWave));
-    if (keep_rng) hipLaunchKernelGGL((k_fork<1, true>), grid, dim3(kWave), 0, s, dst, f);
-    else if (waves == 1) hipLaunchKernelGGL((k_fork<1, false>), grid, dim3(kWave), 0, s, dst, f);
-    else if (waves == 4) hipLaunchKernelGGL((k_fork<4, false>), grid, dim3(4 * kWave), 0, s, dst, f);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-#elif defined(ST_STEP_PACKED_TU)
-// st_step's packed-obs launches (every k_step<.., F32 = false, ..>: the
-// prologue-draw schedule, step_draw_once); launch_step keeps the float32 ones
-hipError_t launch_step_packed(const KParams &p, hipStream_t s) {
-    const dim3 grid((unsigned)(p.stride / kWave)), block(2 * kWave);  // logic + draw wave
-    const bool sc0 = !(p.flags & kScoringFlags);
-    if (p.final_obs || p.info || p.gate) {  // st_step_vec: the vector env's outputs (VEC); gated launches
-        if (p.W == 10 && p.H == 20) {
-            if (sc0) hipLaunchKernelGGL((k_step<10, 20, false, false, true, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-            else hipLaunchKernelGGL((k_step<10, 20, false, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-        } else {
-            hipLaunchKernelGGL((k_step<0, 0, false, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-        }
-    } else if (p.stamps && p.W == 10 && p.H == 20) {
-        if (sc0) hipLaunchKernelGGL((k_step<10, 20, false, true, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-        else hipLaunchKernelGGL((k_step<10, 20, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-    } else if (p.W == 10 && p.H == 20) {
-        if (sc0) hipLaunchKernelGGL((k_step<10, 20, false, false, true>), grid, block, 0, s, ST_STEP_ARGS(p));
-        else hipLaunchKernelGGL((k_step<10, 20, false>), grid, block, 0, s, ST_STEP_ARGS(p));
-    } else {
-        hipLaunchKernelGGL((k_step<0, 0, false>), grid, block, 0, s, ST_STEP_ARGS(p));
-    }
-    return hipGetLastError();
-}
-#else  // the library's own translation unit
 
 hipError_t launch_seed(const KParams &p, hipStream_t s) {
     const int64_t blocks = (p.stride + 255) / 256;
@@ -6946,6 +4332,5 @@ hipError_t launch_export(const KParams &p, int64_t env, const uint32_t *obs, con
     return hipGetLastError();
 }
 
-#endif  // the library's own translation unit
-
 }  // namespace st
+#endif  // !ST_SIDE_TU

@@ -1,8 +1,10 @@
 """TetrisBatch: N independent SimpleTetris engines resident on one MI355X.
 
-Host mirror of TetrisEngine (/root/reference/gym_simpletetris/envs/tetris_env.py:125-335)
+Host mirror of TetrisEngine (the reference's gym_simpletetris/envs/tetris_env.py:125-335)
 for N envs at once.  All game logic runs in the HIP kernels of
-libsimpletetris.so (csrc/st_kernels.hip); this class only owns the context,
+libsimpletetris.so (csrc/: the core and the library's own kernels in
+st_kernels.hip, every planner family in a unit of its own beside it, the C
+ABI in st_capi.cpp); this class only owns the context,
 the output buffers (torch tensors on the device) and the stream plumbing.
 """
 from __future__ import annotations

@@ -86,6 +86,23 @@ def test_library_is_gfx950_code_object():
     assert b"k_step" in data
 
 
+def test_kernel_units_are_listed_once_and_share_one_switch():
+    """Every csrc/*.hip is a unit of the Makefile's UNITS list and vice versa,
+    and the only translation-unit switch in csrc/ is ST_SIDE_TU: a unit owns
+    its text, st_kernels.hip does not grow per-unit #if arms again."""
+    csrc = os.path.join(ROOT, "gym-simpletetris_amd", "csrc")
+    lines = [l for l in open(os.path.join(csrc, "Makefile")).read().split("\n") if re.match(r"UNITS\s*:?=", l)]
+    assert len(lines) == 1, lines
+    units = lines[0].split("=", 1)[1].split()
+    assert len(units) == len(set(units)) and "st_kernels" in units
+    assert sorted(u + ".hip" for u in units) == sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    for f in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, f)
+        if os.path.isfile(path):
+            words = set(re.findall(r"\w*_TU\w*", open(path, errors="replace").read()))
+            assert words <= {"ST_SIDE_TU"}, (f, words)
+
+
 def test_no_cpu_fallback():
     import gym_simpletetris_amd as G
     if torch.cuda.is_available():

@@ -43,7 +43,7 @@ sys.path.insert(0, os.path.join(ROOT, "gym-simpletetris_amd"))
 from gym_simpletetris_amd import BCTS_WEIGHTS, DELLACHERIE_WEIGHTS, GREEDY_WEIGHTS, TetrisBatch, _lib as C  # noqa: E402
 from gym_simpletetris_amd.engine import _ptr, weight_rows  # noqa: E402
 
-# the piece table (T J L Z S I O) and its rotation rule, as in st_kernels.hip
+# the piece table (T J L Z S I O) and its rotation rule, as in csrc/st_kernels.hip's core (kShapes)
 SHAPES = (((0, 0), (-1, 0), (1, 0), (0, -1)), ((0, 0), (-1, 0), (0, -1), (0, -2)),
           ((0, 0), (1, 0), (0, -1), (0, -2)), ((0, 0), (-1, 0), (0, -1), (1, -1)),
           ((0, 0), (-1, -1), (0, -1), (1, 0)), ((0, 0), (0, -1), (0, -2), (0, -3)),

@@ -1,16 +1,20 @@
-"""Static comparison of two builds of st_kernels.hip, kernel by kernel.
+"""Static comparison of two builds of the kernel units, kernel by kernel.
 
-usage: python tools/isa_cmp.py before.s before_resource.txt after.s after_resource.txt
+usage: python tools/isa_cmp.py before.s before_resource.txt after.s after_resource.txt [four more per unit ...]
 
-The .s files are `make asm` outputs, the resource files `make resource`
-outputs.  Per kernel of the step / rollout / render / policy families: the
-instruction total and its valu / salu / lds / vmem split (tools/isa_segs.py's
-classes), VGPRs, SGPRs, occupancy, LDS size and scratch size, before -> after,
-and whether the instruction streams are equal as text (comments, directives
-and labels stripped, label references renumbered away).  Every other kernel
-is only checked for an equal stream.  The last lines state the conditions a
-refactor has to meet: scratch stays 0, occupancy does not drop, LDS size is
-unchanged.
+The .s files are `make asm` outputs (build/<unit>.s), the resource files
+`make resource` outputs -- of the one unit or of all of them, kernels are
+found by name.  One report per group of four, headed `== <unit>` when there
+are several.  Per kernel of the step / rollout / render / policy families:
+the instruction total and its valu / salu / lds / vmem split
+(tools/isa_segs.py's classes), VGPRs, SGPRs, occupancy, LDS size and scratch
+size, before -> after, and whether the instruction streams are equal as text
+(comments, directives and labels stripped, label references renumbered
+away).  Every other kernel is checked for an equal stream and equal
+resources.  The last lines state the conditions a refactor has to meet, for
+every kernel: it exists on both sides (a unit that gained or lost an
+instantiation shows up), scratch stays 0, occupancy does not drop, LDS size
+is unchanged.  The exit status is 1 if any group violates one.
 """
 import collections
 import re
@@ -72,19 +76,34 @@ def demangle(names):
     return dict(zip(names, r.stdout.split('\n')))
 
 
+def short_name(full):
+    return re.sub(r'\(.*$', '', re.sub(r'^(void )?st::\(anonymous namespace\)::', '', full))
+
+
 def main(pa, pr, na, nr):
     ka, kb, ra, rb = kernels(pa), kernels(na), resources(pr), resources(nr)
     names = [n for n in ka if n in ra]
-    dm = demangle(names)
-    bad, same_n, diff_n, other_same, other_diff = [], 0, 0, 0, []
+    added = [n for n in kb if n in rb and n not in names]
+    dm = demangle(names + added)
+    bad, same_n, diff_n, other_same, other_diff, res_diff = [], 0, 0, 0, [], []
+    only = ['%s (before only)' % short_name(dm[n]) for n in names if n not in kb or n not in rb]
+    only += ['%s (after only)' % short_name(dm[n]) for n in added]
     print('kernel | instructions: total valu/salu/lds/vmem, before -> after | '
           'VGPRs SGPRs occupancy LDS scratch, before -> after | stream')
     for n in names:
-        short = re.sub(r'\(.*$', '', re.sub(r'^(void )?st::\(anonymous namespace\)::', '', dm[n]))
+        short = short_name(dm[n])
         if n not in kb or n not in rb:
-            bad.append(short + ' missing')
             continue
         same = ka[n] == kb[n]
+        x, y = ra[n], rb[n]
+        if any(x.get(k) != y.get(k) for k in KEYS):
+            res_diff.append(short)
+        if x.get('ScratchSize') == 0 and y.get('ScratchSize') != 0:
+            bad.append(short + ' scratch')
+        if y.get('Occupancy', 0) < x.get('Occupancy', 0):
+            bad.append(short + ' occupancy')
+        if y.get('LDS') != x.get('LDS'):
+            bad.append(short + ' LDS size')
         if short.split('<')[0] not in FAMILIES:
             other_same += same
             if not same:
@@ -92,24 +111,29 @@ def main(pa, pr, na, nr):
             continue
         same_n += same
         diff_n += not same
-        x, y = ra[n], rb[n]
         print('%s | %d %d/%d/%d/%d -> %d %d/%d/%d/%d | %s -> %s | %s' % (
             (short,) + mix(ka[n]) + mix(kb[n]) + (' '.join(str(x.get(k)) for k in KEYS),
                                                 ' '.join(str(y.get(k)) for k in KEYS),
                                                 'identical' if same else 'differs')))
-        if x.get('ScratchSize') == 0 and y.get('ScratchSize') != 0:
-            bad.append(short + ' scratch')
-        if y.get('Occupancy', 0) < x.get('Occupancy', 0):
-            bad.append(short + ' occupancy')
-        if y.get('LDS') != x.get('LDS'):
-            bad.append(short + ' LDS size')
     print('listed kernels: %d identical streams, %d differ' % (same_n, diff_n))
     print('other kernels: %d identical streams, %d differ%s' % (
         other_same, len(other_diff), ': ' + ', '.join(other_diff) if other_diff else ''))
-    print('scratch stays 0, occupancy does not drop, LDS size unchanged: %s' % (
+    print('VGPRs, SGPRs, occupancy, LDS size, scratch of every kernel: %s' % (
+        'equal' if not res_diff else 'differ for ' + ', '.join(res_diff)))
+    bad = only + bad
+    print('kernels on one side only: %s' % (', '.join(only) if only else 'none'))
+    print('no kernel on one side only, scratch stays 0, occupancy does not drop, LDS size unchanged: %s' % (
         'all hold' if not bad else 'VIOLATED: ' + ', '.join(bad)))
     return 1 if bad else 0
 
 
 if __name__ == '__main__':
-    sys.exit(main(*sys.argv[1:5]))
+    args = sys.argv[1:]
+    if not args or len(args) % 4:
+        sys.exit(__doc__)
+    status = 0
+    for i in range(0, len(args), 4):
+        if len(args) > 4:
+            print('== ' + re.sub(r'^.*/|\.s$', '', args[i + 2]))
+        status |= main(*args[i:i + 4])
+    sys.exit(status)

@@ -1,5 +1,7 @@
 """Static instruction mix of one kernel's loops, from the device assembly
-(`make -C gym-simpletetris_amd/csrc asm` -> build/st_kernels.s).
+(`make -C gym-simpletetris_amd/csrc asm` -> build/<unit>.s, one file per unit
+of the Makefile's UNITS: build/st_kernels.s holds the library's own kernels,
+build/st_routes.s k_routes, and so on -- the table heading st_kernels.hip).
 
 For the kernel whose mangled name contains every given substring, prints
 each loop (a backward branch to an earlier label) with the static count of
@@ -9,7 +11,8 @@ counted inside their parents too), and the kernel totals.  Static counts:
 straight-line code is what a wave issues once per iteration; branches that
 skip blocks make the dynamic count smaller.
 
-usage: python tools/isa_loops.py build/st_kernels.s k_rollout Li10ELi20ELb0ELb1ELb0E
+usage: python tools/isa_loops.py build/<unit>.s <name substrings ...>
+  e.g. python tools/isa_loops.py build/st_kernels.s k_rollout Li10ELi20ELb0ELb1ELb0E
 """
 import re
 import sys

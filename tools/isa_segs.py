@@ -1,6 +1,10 @@
 """Instruction mix of a kernel's ISA per s_memtime segment (stamp builds).
 
-usage: python tools/isa_segs.py build/st_kernels.s <mangled-kernel-name> [seg-to-print]
+usage: python tools/isa_segs.py build/<unit>.s <mangled-kernel-name> [seg-to-print]
+
+<unit>.s is the `make asm` output of the unit that instantiates the kernel
+(build/st_kernels.s: the float32 k_step, k_rollout, k_rollout2;
+build/st_step_packed.s: the packed-obs k_step).
 """
 import collections
 import sys
