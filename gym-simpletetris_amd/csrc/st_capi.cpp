@@ -45,6 +45,11 @@ struct st_ctx {
     // [ST_ROUTE_WORDS][n], slot (st_play_locks: lock position), steps and rem
     // int32 [n]
     int32_t *play_buf;
+    // st_ntuple_set: the network's descriptors int32 [nt_T][6] (device), its tuple count (0: no network) and
+    // table length
+    int32_t *nt_desc;
+    int32_t nt_T;
+    int64_t nt_len;
 };
 
 namespace {
@@ -113,6 +118,10 @@ void free_state(st_ctx *c) {
     if (c->gate_ev) (void)hipEventDestroy(c->gate_ev);
     if (c->play_buf) (void)hipFree(c->play_buf);
     c->play_buf = nullptr;
+    if (c->nt_desc) (void)hipFree(c->nt_desc);
+    c->nt_desc = nullptr;
+    c->nt_T = 0;
+    c->nt_len = 0;
     c->gate = c->gate_host = c->gate_host_dev = nullptr;
     c->gate_ev = nullptr;
     c->stamps = nullptr;
@@ -658,16 +667,24 @@ struct PlayRouted {
     int32_t *pieces;
     bool locks = false;
 };
+// ntuple: st_play_ntuple -- the policy is the n-tuple kernel (d_weights its first-ply rows or null), committing its
+// own choice
+struct PlayNtuple {
+    const float *table;
+    float dead_value;
+};
 static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weights, int64_t n_w, int64_t k,
                      int64_t *d_return, int32_t *d_episodes, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
                      st_stream stream, int32_t set = ST_FEATS_BASE, const PlayLookahead *look = nullptr,
-                     const PlayRouted *routed = nullptr) {
-    if (!c || !d_weights) return fail(ST_EINVAL, "%s: null argument", fn);
+                     const PlayRouted *routed = nullptr, const PlayNtuple *ntuple = nullptr) {
+    if (!c || (ntuple ? !ntuple->table : !d_weights)) return fail(ST_EINVAL, "%s: null argument", fn);
     if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS) return fail(ST_EINVAL, "%s: unknown feature set %d", fn, set);
-    if (n_w < 1) return fail(ST_EINVAL, "%s: n_w %lld < 1", fn, (long long)n_w);
+    if (n_w < 1 && d_weights) return fail(ST_EINVAL, "%s: n_w %lld < 1", fn, (long long)n_w);
     if (look && !std::isfinite(look->dead_value)) return fail(ST_EINVAL, "%s: dead_value is not finite", fn);
+    if (ntuple && !std::isfinite(ntuple->dead_value)) return fail(ST_EINVAL, "%s: dead_value is not finite", fn);
     if (routed && c->cfg.lock_delay > ST_REACH_MAX_LOCK)
         return fail(ST_EINVAL, "%s: lock_delay %d > %d", fn, c->cfg.lock_delay, ST_REACH_MAX_LOCK);
+    if (ntuple && c->nt_T < 1) return fail(ST_ESTATE, "%s without a network (st_ntuple_set)", fn);
     if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "%s before st_seed + st_reset", fn);
     if (k <= 0) return ST_OK;
     DeviceGuard g(c->device);
@@ -694,7 +711,11 @@ static int play_impl(st_ctx *c, const char *fn, bool commit, const float *d_weig
                 ST_HIP(st::launch_routes(params(c), set, d_weights, n_w, nullptr, nullptr, q.plan_rem, q.plan_slot,
                                          q.plan_route, q.plan_steps, nullptr, s));
             ST_HIP(st::launch_route_pop(params(c), q.plan_route, q.plan_steps, q.plan_rem, q.act, routed->pieces, s));
-        } else if (look && look->expect)
+        } else if (ntuple)
+            ST_HIP(st::launch_policy_ntuple(params(c), set, true, d_weights, n_w, c->nt_desc, c->nt_T, ntuple->table,
+                                            ntuple->dead_value, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                            nullptr, nullptr, s));
+        else if (look && look->expect)
             ST_HIP(st::launch_policy_expect(params(c), set, true, look->weights1, d_weights, n_w, look->dead_value,
                                             nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s));
         else if (look)
@@ -967,6 +988,99 @@ int st_play_locks(st_ctx *c, int32_t set, const float *d_weights, int64_t n_w, i
     routed.locks = true;
     return play_impl(c, "st_play_locks", false, d_weights, n_w, k, d_return, d_episodes, d_obs, d_reward, d_done,
                      stream, set, nullptr, &routed);
+}
+
+int st_ntuple_set(st_ctx *c, const int32_t *tuples_host, int32_t T) {
+    if (!c) return fail(ST_EINVAL, "st_ntuple_set: null context");
+    if (T < 0 || T > st::kNtMaxT)
+        return fail(ST_EINVAL, "st_ntuple_set: T %d outside [0, %d]", T, st::kNtMaxT);
+    if (T > 0 && !tuples_host) return fail(ST_EINVAL, "st_ntuple_set: null tuples");
+    const int W = c->cfg.width, H = c->cfg.height;
+    int64_t len = 0;
+    for (int32_t t = 0; t < T; ++t) {
+        const int32_t *d = tuples_host + 6 * (int64_t)t;
+        const int64_t x = d[0], y = d[1], w = d[2], h = d[3], flip = d[4], base = d[5];
+        const char *bad = w < 1 || h < 1                  ? "w or h < 1"
+                          : w * h > ST_NTUPLE_MAX_BITS    ? "more than 16 cells"
+                          : x < 0 || x + w > W            ? "columns off the board"
+                          : y < 0 || y + h > H            ? "rows off the board"
+                          : flip != 0 && flip != 1        ? "flip not 0 or 1"
+                          : base < 0                      ? "negative base"
+                          : base + (int64_t(1) << (w * h)) > INT32_MAX ? "table_len above 2^31 - 1"
+                                                          : nullptr;
+        if (bad)
+            return fail(ST_EINVAL, "st_ntuple_set: tuple %d (x %d, y %d, w %d, h %d, flip %d, base %d) on a %dx%d board: %s",
+                        t, d[0], d[1], d[2], d[3], d[4], d[5], W, H, bad);
+        len = std::max(len, base + (int64_t(1) << (w * h)));
+    }
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_ntuple_set: hipSetDevice(%d) failed", c->device);
+    int32_t *desc = nullptr;
+    if (T > 0) {
+        const size_t bytes = (size_t)T * 6 * sizeof(int32_t);
+        hipError_t e = hipMalloc(&desc, bytes);
+        if (e != hipSuccess) return fail(ST_ENOMEM, "st_ntuple_set: hipMalloc failed: %s", hipGetErrorString(e));
+        e = hipMemcpy(desc, tuples_host, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(desc);
+            return hip_fail(e, "st_ntuple_set: uploading the descriptors");
+        }
+    }
+    if (c->nt_desc) {  // (launches that read the old descriptors may still be queued)
+        (void)hipDeviceSynchronize();
+        (void)hipFree(c->nt_desc);
+    }
+    c->nt_desc = desc;
+    c->nt_T = T;
+    c->nt_len = len;
+    return ST_OK;
+}
+
+int64_t st_ntuple_table_len(const st_ctx *c) { return c ? c->nt_len : 0; }
+
+int st_ntuple_eval(st_ctx *c, const float *d_table, const uint32_t *d_boards, int64_t m, float *d_values,
+                   int32_t *d_index, st_stream stream) {
+    if (!c || !d_table) return fail(ST_EINVAL, "st_ntuple_eval: null argument");
+    if (!d_values && !d_index) return fail(ST_EINVAL, "st_ntuple_eval: every output is null");
+    if (d_boards && m < 0) return fail(ST_EINVAL, "st_ntuple_eval: m %lld < 0", (long long)m);
+    if (c->nt_T < 1) return fail(ST_ESTATE, "st_ntuple_eval without a network (st_ntuple_set)");
+    if (!d_boards && (!c->seeded || !c->reset_once))
+        return fail(ST_ESTATE, "st_ntuple_eval of the context's boards before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_ntuple_eval: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_ntuple_eval(c->nt_desc, c->nt_T, d_table, d_boards ? d_boards : c->board,
+                                  d_boards ? m : c->stride, d_boards ? m : c->n, d_values, d_index,
+                                  (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_policy_ntuple(st_ctx *c, int32_t set, const float *d_weights, int64_t n_w, const float *d_table,
+                     float dead_value, const int32_t *d_allowed, int32_t *d_slots, uint8_t *d_actions,
+                     float *d_scores, float *d_values, int32_t *d_best, int32_t *d_index, float *d_values_all,
+                     st_stream stream) {
+    if (!c || !d_table) return fail(ST_EINVAL, "st_policy_ntuple: null argument");
+    if (set != ST_FEATS_BASE && set != ST_FEATS_BCTS)
+        return fail(ST_EINVAL, "st_policy_ntuple: unknown feature set %d", set);
+    if (d_weights && n_w < 1) return fail(ST_EINVAL, "st_policy_ntuple: n_w %lld < 1", (long long)n_w);
+    if (!d_slots && !d_actions && !d_scores && !d_values && !d_best && !d_index && !d_values_all)
+        return fail(ST_EINVAL, "st_policy_ntuple: every output is null");
+    if (!std::isfinite(dead_value)) return fail(ST_EINVAL, "st_policy_ntuple: dead_value is not finite");
+    if (c->nt_T < 1) return fail(ST_ESTATE, "st_policy_ntuple without a network (st_ntuple_set)");
+    if (!c->seeded || !c->reset_once) return fail(ST_ESTATE, "st_policy_ntuple before st_seed + st_reset");
+    DeviceGuard g(c->device);
+    if (!g.ok) return fail(ST_EHIP, "st_policy_ntuple: hipSetDevice(%d) failed", c->device);
+    ST_HIP(st::launch_policy_ntuple(params(c), set, false, d_weights, n_w, c->nt_desc, c->nt_T, d_table, dead_value,
+                                    d_allowed, d_slots, d_actions, d_scores, d_values, d_best, d_index, d_values_all,
+                                    (hipStream_t)stream));
+    return ST_OK;
+}
+
+int st_play_ntuple(st_ctx *c, int32_t set, const float *d_weights, int64_t n_w, const float *d_table,
+                   float dead_value, int64_t k, int64_t *d_return, int32_t *d_episodes, uint32_t *d_obs,
+                   int32_t *d_reward, uint8_t *d_done, st_stream stream) {
+    const PlayNtuple nt{d_table, dead_value};
+    return play_impl(c, "st_play_ntuple", true, d_weights, n_w, k, d_return, d_episodes, d_obs, d_reward, d_done,
+                     stream, set, nullptr, nullptr, &nt);
 }
 
 int st_place(st_ctx *c, const int32_t *d_slots, uint8_t *d_placed, st_stream stream) {

@@ -12,6 +12,7 @@ constexpr int kPad = 4;        // wall columns on each side of the LDS board
 constexpr int kMaxW = 32;
 constexpr int kMaxH = 28;
 constexpr int kMtN = 624;
+constexpr int kNtMaxT = 4096;  // simpletetris.h's limit on the tuples of an n-tuple network (st_ntuple_set)
 // Per-env MT storage (words): generation buffers A and B, then a 16-word pad
 // (see st_kernels.hip, "Double-buffered twist"); 16-B aligned.
 constexpr int64_t kMtPitch = 2 * kMtN + 16;
@@ -163,6 +164,17 @@ hipError_t launch_afterstates_at(const KParams &p, int set, const int32_t *pos, 
 hipError_t launch_locks(const KParams &p, int set, const float *weights, int64_t n_w, const int32_t *pos_in,
                         const uint8_t *need, int32_t *rem, int32_t *pos, uint64_t *route, int32_t *steps,
                         float *scores, int32_t *best, int32_t *count, hipStream_t s);
+// st_ntuple_eval (st_ntuple.hip): desc int32 [T][6] (validated by st_ntuple_set), table float [table_len], boards
+// uint32 [W][pitch] with m boards in use -> values float [m], index int32 [T][m], either null; m <= 0: no launch
+hipError_t launch_ntuple_eval(const int32_t *desc, int T, const float *table, const uint32_t *boards, int64_t pitch,
+                              int64_t m, float *values, int32_t *index, hipStream_t s);
+// st_policy_ntuple / st_play_ntuple (commit: the chosen slot is committed like launch_place): weights float
+// [n_w][rows of set] or null, allowed int32 [n][S] or null; slots int32 [n], actions uint8 [n], scores / values float
+// [n], best int32 [rows][n], index int32 [T][n], values_all float [n][S], any null
+hipError_t launch_policy_ntuple(const KParams &p, int set, bool commit, const float *weights, int64_t n_w,
+                                const int32_t *desc, int T, const float *table, float dead_value,
+                                const int32_t *allowed, int32_t *slots, uint8_t *actions, float *scores, float *values,
+                                int32_t *best, int32_t *index, float *values_all, hipStream_t s);
 // st_fork: dst env e takes the state of src env index[e] (index int32 [dst.n] or null: e) where mask[e] != 0 (mask
 // uint8 [dst.n] or null: every env) and the index lies in [0, src.n); keep_rng: the MT19937 state stays dst's own.
 // waves: the deep copy's waves per 64 envs, 1 or 4

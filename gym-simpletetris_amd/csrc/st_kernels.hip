@@ -44,6 +44,7 @@
 //   st_routes.hip       k_routes, k_route_pop
 //   st_locks.hip        k_lock_set, k_afterstates_at, k_locks
 //   st_fork.hip         k_fork
+//   st_ntuple.hip       k_ntuple_eval, k_policy_ntuple
 #include "st_internal.h"
 
 namespace st {

@@ -10,8 +10,9 @@ is importable the ids are registered there too.
 import os as _os
 
 from .engine import (BCTS_WEIGHTS, DELLACHERIE_WEIGHTS, GREEDY_WEIGHTS, SHAPE_NAMES, Afterstates,  # noqa: F401
-                     ExpectChoice, LinearChoice, LockChoice, LockSet, LookaheadChoice, Reachable, RoutedChoice, Routes,
-                     TetrisBatch, lock_pos, lock_rot_x_y, route_pack, route_unpack)
+                     ExpectChoice, LinearChoice, LockChoice, LockSet, LookaheadChoice, NTupleChoice, Reachable, RoutedChoice,
+                     Routes, TetrisBatch, lock_pos, lock_rot_x_y, route_pack, route_unpack)
+from .ntuple import NTupleNet, td_update  # noqa: F401
 from .envs import TetrisEngine, TetrisEnv, TetrisVecEnv  # noqa: F401
 
 __version__ = "0.1.0"

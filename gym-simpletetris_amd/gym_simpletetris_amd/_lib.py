@@ -51,6 +51,7 @@ FEATURE_NAMES = {"base": AFTER, "bcts": AFTER_BCTS}  # feature set -> its rows b
 REACH_MAX_LOCK = 3  # ST_REACH_MAX_LOCK: the largest lock_delay st_reachable / st_route_actions take
 ROUTE_MAX, ROUTE_WORDS = 42, 2  # ST_ROUTE_MAX, ST_ROUTE_WORDS: a packed route's actions and uint64 words
 FORK_KEEP_RNG = 1 << 0  # st_fork_flags: ST_FORK_KEEP_RNG
+NTUPLE_MAX_TUPLES, NTUPLE_MAX_BITS = 4096, 16  # ST_NTUPLE_MAX_TUPLES, ST_NTUPLE_MAX_BITS
 
 
 class StError(RuntimeError):
@@ -145,6 +146,12 @@ SIG = {
     "st_routes_at": ([_vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_policy_locks": ([_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_play_locks": ([_vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
+    "st_ntuple_set": ([_vp, _vp, _i32], ctypes.c_int),
+    "st_ntuple_table_len": ([_vp], _i64),
+    "st_ntuple_eval": ([_vp, _vp, _vp, _i64, _vp, _vp, _vp], ctypes.c_int),
+    "st_policy_ntuple": ([_vp, _i32, _vp, _i64, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+                         ctypes.c_int),
+    "st_play_ntuple": ([_vp, _i32, _vp, _i64, _vp, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),
     "st_debug_stamps": ([_vp, _vp, _i64], ctypes.c_int),
     "st_last_error": ([], ctypes.c_char_p),
     "st_abi_version": ([], ctypes.c_int),
@@ -180,7 +187,7 @@ def load(path: str = LIB_PATH):
                 continue
             # an addition that did not change the ABI number (st_step_export, st_afterstates,
             # st_policy_linear, st_place, st_reachable, st_afterstates_set, st_next_piece, st_routes,
-            # st_fork, st_next_weights, st_lock_set):
+            # st_fork, st_next_weights, st_lock_set, st_ntuple_set):
             # the library on disk was built before it
             raise ImportError(f"{path}: no symbol {name} (a stale build of ABI {abi}: rebuild it with "
                               "`make -C gym-simpletetris_amd/csrc`)")

@@ -378,6 +378,21 @@ class LinearChoice:
         return feat[row]
 
 
+class NTupleChoice(LinearChoice):
+    """TetrisBatch.policy_ntuple()'s result: LinearChoice's `slots`, `actions`,
+    `scores` and `feat` (with its rows by name), and `values` float32 [n] (V of
+    the chosen slot: the network's value of its afterstate board, dead_value
+    where it ends the game, 0 without a slot); with index=True `index` int32
+    [T, n] (the table entries the value was read from, env innermost; -1 rows
+    where no slot was chosen or the chosen slot is dead) and with
+    values_all=True `values_all` float32 [n, S] (V of every candidate, 0.0
+    elsewhere), else None.  A field not asked for (`out`) is None."""
+
+    def __init__(self, slots, actions, scores, feat, values=None, index=None, values_all=None):
+        super().__init__(slots, actions, scores, feat)
+        self.values, self.index, self.values_all = values, index, values_all
+
+
 class LookaheadChoice:
     """TetrisBatch.policy_lookahead()'s result: `slots` int32 [n] (the chosen
     first-ply slot, -1: no candidate), `slots2` int32 [n] (the best second-ply
@@ -499,6 +514,7 @@ class TetrisBatch:
         self._route_act: Optional[torch.Tensor] = None  # route_actions' reused output (made on first use)
         self.placed: Optional[torch.Tensor] = None  # place() / step_placements(): uint8 [n] commit flags (made on first use)
         self._fork_groups: dict = {}  # fork_groups' (index, mask) device tensors by group size
+        self._ntuple = None  # set_ntuple's network (the library holds its own copy of the tuples)
         self._seeded = False
         if seeds is not None:
             self.seed(seeds)
@@ -1701,6 +1717,152 @@ class TetrisBatch:
             else _check_out(out, self.width, self.n, self.device)
         C.check(self._L.st_play_expect(self._ctx, fset, _ptr(w1), _ptr(w2), w2.shape[0], dv, int(k),
                                        _ptr(returns), _ptr(episodes), _ptr(o_t) if obs == "packed" else None,
+                                       _ptr(r_t), _ptr(d_t), self._stream()))
+        return returns, episodes
+
+    # ------------------------------------------------------------ n-tuple network
+    def set_ntuple(self, net) -> None:
+        """Give the batch its n-tuple network (st_ntuple_set): an
+        ntuple.NTupleNet of the batch's board size, or None to remove it.  The
+        library validates the tuples again and keeps a device copy of its own;
+        a later call replaces it.  Synchronous."""
+        if net is None:
+            C.check(self._L.st_ntuple_set(self._ctx, None, 0))
+            self._ntuple = None
+            return
+        if (net.width, net.height) != (self.width, self.height):
+            raise ValueError(f"net: a {net.width}x{net.height} network on a {self.width}x{self.height} batch")
+        t = np.ascontiguousarray(net.tuples, np.int32)
+        C.check(self._L.st_ntuple_set(self._ctx, t.ctypes.data_as(ctypes.c_void_p), len(t)))
+        assert self._L.st_ntuple_table_len(self._ctx) == net.table_len
+        self._ntuple = net
+
+    def _ntuple_table(self, table) -> torch.Tensor:
+        """The host layer's check of a table: a contiguous float32 tensor on
+        the batch's device with at least table_len entries."""
+        net = getattr(self, "_ntuple", None)
+        if net is None:
+            raise RuntimeError("no n-tuple network: call set_ntuple(net) first")
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.device != self.device \
+                or not table.is_contiguous():
+            raise ValueError(f"table: a contiguous float32 tensor on {self.device} is needed")
+        if table.numel() < net.table_len:
+            raise ValueError(f"table: {table.numel()} entries, the network needs {net.table_len}")
+        return table
+
+    def ntuple_eval(self, table, boards: Optional[torch.Tensor] = None, index: bool = False, out=None):
+        """The network's value of boards (st_ntuple_eval): float32 sum of the
+        T table entries in tuple order.  boards: None for the batch's own
+        boards (values [n]), or a contiguous int32 device tensor [W, ...] of
+        packed column words (the obs layout; afterstates().boards permuted
+        to [W, n, S]) -- values take the shape behind W.  With index=True
+        returns (values, index), index int32 [T, ...]: the entries read.
+        `out`: a (values, index) pair of device tensors to write, None for the
+        one not wanted; the pair is returned."""
+        table = self._ntuple_table(table)
+        T = len(self._ntuple)
+        if boards is None:
+            rest, m = (self.n,), self.n
+        else:
+            if not isinstance(boards, torch.Tensor) or boards.dtype != torch.int32 or boards.device != self.device \
+                    or boards.dim() < 2 or boards.shape[0] != self.width or not boards.is_contiguous():
+                raise ValueError(f"boards: a contiguous int32 [{self.width}, ...] tensor on {self.device} is needed")
+            rest = tuple(boards.shape[1:])
+            m = int(np.prod(rest))
+        if out is None:
+            values = torch.empty(rest, dtype=torch.float32, device=self.device)
+            idx = torch.empty((T,) + rest, dtype=torch.int32, device=self.device) if index else None
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[0] is None and out[1] is None):
+                raise ValueError("out: a (values, index) pair, None for an output not wanted (not both)")
+            values, idx = out
+            if values is not None:
+                _check_tensor(values, "out values", rest, (torch.float32,), self.device)
+            if idx is not None:
+                _check_tensor(idx, "out index", (T,) + rest, (torch.int32,), self.device)
+        C.check(self._L.st_ntuple_eval(self._ctx, _ptr(table), _ptr(boards), m, _ptr(values), _ptr(idx),
+                                       self._stream()))
+        return (values, idx) if index or out is not None else values
+
+    def policy_ntuple(self, table, weights=None, dead_value: float = 0.0, features: str = "base", allowed=None,
+                      index: bool = False, values_all: bool = False, out=None) -> NTupleChoice:
+        """policy_linear with the n-tuple network behind it, in one launch
+        (st_policy_ntuple).  Every candidate slot of the current piece (valid,
+        and allowed where `allowed` is given: policy_linear's mask) scores
+        S1 + V in float32: S1 the chain score of its rows under `weights` (as
+        policy_linear takes them; None: 0), V the network's value of its
+        afterstate board (afterstates().boards) read from `table`, or
+        `dead_value` where the placement ends the game.  The candidate with
+        the largest score wins, ties to the lowest slot.  With the 'reward'
+        weight 1 and every other 0 that is the TD afterstate rule
+        argmax r + V(s').  Returns an NTupleChoice: .slots (-1: no candidate,
+        then action 2, score 0, value 0), .actions, .scores, .feat, .values,
+        and .index (index=True) / .values_all (values_all=True).  Reads the
+        state, changes none of it.  `out`: a (slots, actions, scores, feat,
+        values) tuple, with index / values_all tensors behind it where those
+        are asked for; None entries are not computed (at least one is needed)."""
+        n, S = self.n, self.n_slots
+        table = self._ntuple_table(table)
+        T = len(self._ntuple)
+        fset, nrows, _ = _feature_set(features)
+        w = None if weights is None else self._weights(weights, features)
+        dv = _dead_value(dead_value)
+        if isinstance(allowed, Reachable):
+            allowed = allowed.steps
+        if allowed is not None:
+            _check_tensor(allowed, "allowed", (n, S), (torch.int32,), self.device)
+        spec = [("slots", (n,), torch.int32), ("actions", (n,), torch.uint8), ("scores", (n,), torch.float32),
+                ("feat", (nrows, n), torch.int32), ("values", (n,), torch.float32)]
+        if index:
+            spec.append(("index", (T, n), torch.int32))
+        if values_all:
+            spec.append(("values_all", (n, S), torch.float32))
+        if out is None:
+            out = tuple(torch.empty(sh, dtype=dt, device=self.device) for _, sh, dt in spec)
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != len(spec):
+                raise ValueError(f"out: a ({', '.join(s[0] for s in spec)}) tuple, None for an output not wanted")
+            if all(t is None for t in out):
+                raise ValueError("out: at least one output tensor is needed")
+            for t, (name, sh, dt) in zip(out, spec):
+                if t is not None:
+                    _check_tensor(t, "out " + name, sh, (dt,), self.device)
+        got = dict(zip((s[0] for s in spec), out))
+        C.check(self._L.st_policy_ntuple(self._ctx, fset, _ptr(w), 0 if w is None else w.shape[0], _ptr(table), dv,
+                                         _ptr(allowed), _ptr(got["slots"]), _ptr(got["actions"]), _ptr(got["scores"]),
+                                         _ptr(got["values"]), _ptr(got["feat"]), _ptr(got.get("index")),
+                                         _ptr(got.get("values_all")), self._stream()))
+        return NTupleChoice(got["slots"], got["actions"], got["scores"], got["feat"], got["values"], got.get("index"),
+                            got.get("values_all"))
+
+    def play_ntuple(self, table, k: int, weights=None, dead_value: float = 0.0, features: str = "base",
+                    returns: Optional[torch.Tensor] = None, episodes: Optional[torch.Tensor] = None,
+                    obs: str = "packed", out=None):
+        """k pieces of policy_ntuple(table, weights, dead_value) ->
+        step_placements(its slots), enqueued by ONE library call
+        (st_play_ntuple), identical to the k rounds by hand: play_lookahead
+        with the network's choice.  `returns` / `episodes`, both autoreset
+        modes, k = 0, obs, `out` and the return value are play_lookahead's."""
+        if obs not in ("packed", "none"):
+            raise ValueError("obs must be 'packed' or 'none'")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+            raise ValueError(f"k must be an integer >= 0, got {k!r}")
+        table = self._ntuple_table(table)
+        fset = _feature_set(features)[0]
+        w = None if weights is None else self._weights(weights, features)
+        dv = _dead_value(dead_value)
+        if returns is None:
+            returns = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        else:
+            _check_tensor(returns, "returns", (self.n,), (torch.int64,), self.device)
+        if episodes is None:
+            episodes = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        else:
+            _check_tensor(episodes, "episodes", (self.n,), (torch.int32,), self.device)
+        o_t, r_t, d_t = (self.obs, self.reward, self.done) if out is None \
+            else _check_out(out, self.width, self.n, self.device)
+        C.check(self._L.st_play_ntuple(self._ctx, fset, _ptr(w), 0 if w is None else w.shape[0], _ptr(table), dv,
+                                       int(k), _ptr(returns), _ptr(episodes), _ptr(o_t) if obs == "packed" else None,
                                        _ptr(r_t), _ptr(d_t), self._stream()))
         return returns, episodes
 

@@ -44,7 +44,8 @@ extern "C" {
  * st_play_lookahead, st_routes / st_policy_routed / st_play_routed,
  * st_fork, st_next_weights / st_policy_expect / st_play_expect, and
  * st_lock_set / st_afterstates_at / st_routes_at / st_policy_locks /
- * st_play_locks.
+ * st_play_locks, and st_ntuple_set / st_ntuple_table_len / st_ntuple_eval /
+ * st_policy_ntuple / st_play_ntuple.
  * Snapshots (st_save) keep their own format version, unchanged. */
 #define ST_ABI_VERSION 4
 
@@ -935,6 +936,89 @@ int st_policy_locks(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_
 int st_play_locks(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w, int64_t k, int64_t *d_return,
                   int32_t *d_episodes, int32_t *d_pieces, uint32_t *d_obs, int32_t *d_reward, uint8_t *d_done,
                   st_stream stream);
+
+/* N-tuple network: a learned, non-linear afterstate value beside the linear
+ * rows -- a set of small windows on the board, each window's bit pattern the
+ * index into a lookup table (the systematic n-tuple networks of the SZ-Tetris
+ * literature, trained by TD on afterstates or by CMA-ES), evaluated on every
+ * placement slot in one launch.
+ *
+ * Network: T tuples, 1 <= T <= ST_NTUPLE_MAX_TUPLES, each six int32
+ *   (x, y, w, h, flip, base): a w x h window whose top-left cell is column x,
+ *   row y (row 0 is the top, as everywhere here), with 1 <= w, 1 <= h,
+ *   w * h <= ST_NTUPLE_MAX_BITS, 0 <= x, x + w <= W, 0 <= y, y + h <= H, flip
+ *   in {0, 1}, base >= 0.  table_len = max over t of base_t + 2^(w_t h_t) must
+ *   be <= 2^31 - 1.  Bases may overlap: tuples then share weights.
+ * Index: on a board B in the layout of st_state_views.board (word c = column c,
+ *   bit r = row r), with i' = flip ? w - 1 - i : i,
+ *     idx_t(B) = sum over i < w of (((B[x + i'] >> y) & (2^h - 1)) << (i * h)).
+ *   A tuple and its mirror image (W - x - w, y, w, h, !flip, base) read mirrored
+ *   boards identically.  Only bits below H are read (host-written garbage above
+ *   row H - 1 plays no part), and every base_t + idx_t lies in [0, table_len).
+ * Value: N(B): acc = 0.0f; for t = 0 .. T - 1 in order acc = acc +
+ *   table[base_t + idx_t(B)] -- float32 adds, each rounded on its own, in this
+ *   order.
+ * Player: st_policy_linear_set with the network behind it.  The slots, their
+ *   validity, the rows f and the CANDIDATE rule with d_allowed are
+ *   st_policy_linear_set's, word for word.  S1(s) is its chain with weight row
+ *   e % n_w; 0.0f if d_weights is NULL (n_w is then ignored).  B(s) is the
+ *   slot's afterstate board -- st_afterstates's d_boards: after _clear_lines,
+ *   before any death erase.  V(s) = N(B(s)) if f[ST_AFTER_DEAD] == 0, else
+ *   dead_value.  score(s) = S1(s) + V(s), one float32 add.  Choice: the
+ *   candidate with the largest score, ties to the lowest slot.  No candidate:
+ *   slot -1, action 2, score 0.0f, value 0.0f, a zero d_best column and an
+ *   all -1 index column.  Weights, dead_value and the table entries that are
+ *   read must be finite; otherwise the result is unspecified, except that the
+ *   slot stays in [-1, S) and nothing faults.  With the ST_AFTER_REWARD row's
+ *   weight 1 and every other weight 0 this is the TD afterstate rule
+ *   argmax r + V(s'). */
+#define ST_NTUPLE_MAX_TUPLES 4096
+#define ST_NTUPLE_MAX_BITS 16
+/* Validates tuples_host (int32 [T][6]) against the context's W, H by the rules
+ * above -- on failure ST_EINVAL with the offending tuple named in
+ * st_last_error, and nothing changes -- and copies the descriptors to device
+ * memory the context owns (freed by st_destroy, replaced by a later call).
+ * T == 0 removes the network.  Synchronous, like st_seed's upload; needs only
+ * st_create. */
+int st_ntuple_set(st_ctx *ctx, const int32_t *tuples_host, int32_t T);
+/* table_len of the context's network, 0 without one (or for a NULL ctx). */
+int64_t st_ntuple_table_len(const st_ctx *ctx);
+/* N of m caller boards d_boards uint32 [W][m]; d_boards NULL: the context's
+ * own boards, m = n_envs (the argument is ignored), read at pitch `stride`.
+ * d_values float [m] or NULL; d_index int32 [T][m] or NULL, base_t + idx_t; not
+ * both NULL.  d_table: float [>= table_len].  One lane per board; reads nothing
+ * else of the context and changes nothing.  ST_EINVAL for a NULL ctx or
+ * d_table, both outputs NULL or m < 0; ST_ESTATE without a network, and with
+ * d_boards NULL before st_seed + st_reset; all before any GPU call. */
+int st_ntuple_eval(st_ctx *ctx, const float *d_table, const uint32_t *d_boards, int64_t m, float *d_values,
+                   int32_t *d_index, st_stream stream);
+/* The player above, one launch.  d_slots, d_actions, d_scores and d_best are
+ * st_policy_linear_set's.  d_values float [n_envs]: V of the chosen slot.
+ * d_index int32 [T][n_envs] (env innermost, like d_best): base_t + idx_t(B(s))
+ * of the chosen slot; -1 in every row where no slot was chosen or the chosen
+ * slot is dead (no table entry was read for it).  d_values_all float
+ * [n_envs][S]: V(s) for every candidate, 0.0f elsewhere.  Each output may be
+ * NULL, but not all seven.  Reads and leaves the state as st_policy_linear_set
+ * does; not gated, needs no st_mt_sync.
+ * Errors, before any GPU call, in this order: ST_EINVAL for a NULL ctx or
+ * d_table, a bad set, n_w < 1 with non-NULL d_weights, all outputs NULL or a
+ * non-finite dead_value; ST_ESTATE without a network; ST_ESTATE before
+ * st_seed + st_reset. */
+int st_policy_ntuple(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w, const float *d_table,
+                     float dead_value, const int32_t *d_allowed, int32_t *d_slots, uint8_t *d_actions,
+                     float *d_scores, float *d_values, int32_t *d_best, int32_t *d_index, float *d_values_all,
+                     st_stream stream);
+/* st_play_lookahead with st_policy_ntuple's choice, at placement level: k times
+ * (st_policy_ntuple, d_allowed NULL, its chosen slot committed by the same
+ * launch -> the step on the constant hard drop), identical to k rounds of
+ * st_policy_ntuple + st_step_placements(d_slots) by hand.  The ring of reward /
+ * done rows and the sums, the first-call rule, the one-buffer-per-context
+ * ordering rule, both autoreset modes, k <= 0 and the last step's d_obs /
+ * d_reward / d_done are st_play_linear_placements's.  Errors as
+ * st_policy_ntuple's (no output rule). */
+int st_play_ntuple(st_ctx *ctx, int32_t set, const float *d_weights, int64_t n_w, const float *d_table,
+                   float dead_value, int64_t k, int64_t *d_return, int32_t *d_episodes, uint32_t *d_obs,
+                   int32_t *d_reward, uint8_t *d_done, st_stream stream);
 
 /* Fork: env states copied on the device, between two contexts or inside one --
  * what a rollout player, a beam search or a population restart needs to put one
